@@ -18,6 +18,13 @@ order double-double sum on the device).  The total work is fixed, so scaling
 is "strong".
 
 Rank 0 prints one JSON line.
+
+A plain run does only what the headline needs: set up, warm up, time the
+steps, write the outputs (``--dump-outputs DIR``), print the line.  Everything
+else the benchmark measures or checks — the reference parity sample, the
+trig-leaf and fp32 variants, the side configs, the evolved / deep-core / cold
+end-to-end legs, the C3 population-sharded leg, the CPU baseline — runs with
+``--full`` (each leg can still be switched off by its ``--no-...`` option).
 """
 import argparse
 import json
@@ -46,6 +53,13 @@ def parse():
     p.add_argument("--seed", type=int, default=2024)
     p.add_argument("--min-depth", type=int, default=4)
     p.add_argument("--max-depth", type=int, default=8)
+    p.add_argument("--full", action="store_true",
+                   help="also run the side measurements and checks (parity "
+                        "sample, trig-leaf and fp32 variants, side configs, "
+                        "evolved / deep-core / cold legs, CPU baseline)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs (hi, lo, err, "
+                        "flags per program) as DIR/<name>.npy, float64")
     p.add_argument("--cpu-trees", type=int, default=0,
                    help="CPU baseline sample (default: 48 trees per worker)")
     p.add_argument("--cpu-cases", type=int, default=65536)
@@ -132,6 +146,29 @@ def parity_sample(hi, lo, err, flags, spec, golden=None):
             "tolerance": 1e-12,
             "source": "tests/golden/c4_bench_sample.json.gz (reference "
                       "gp.compile + symbreg.py:60-61 loop at 2^20 cases)"}
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, out_hi, out_lo, out_err, out_flags):
+    """``--dump-outputs``: what the last timed step left in the caller's four
+    buffers, one value per program, as ``hi.npy``, ``lo.npy`` (the double-
+    double SSE), ``err.npy`` (first failing case, as the unsigned value) and
+    ``flags.npy``, all float64.  Past 64 MB in all, a fixed seeded sample of
+    the programs, its sorted indices in ``index.npy``."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {"hi": out_hi.cpu().numpy(), "lo": out_lo.cpu().numpy(),
+            "err": out_err.cpu().numpy().view(np.uint64),
+            "flags": out_flags.cpu().numpy().view(np.uint32)}
+    n = len(arrs["hi"])
+    keep = DUMP_LIMIT_BYTES // (8 * (len(arrs) + 1))
+    if n > keep:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrs = {k: v[idx] for k, v in arrs.items()}
+        arrs["index"] = idx
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
 
 
 def _oracle_data(name):
@@ -632,11 +669,16 @@ def main():
     progress("headline: timing %d steps" % args.steps)
     elapsed, kernel_ms = timed()
 
+    if args.dump_outputs and rank == 0:
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, out_hi, out_lo, out_err, out_flags)
+
     # parity of the timed launch (after the timed region): the reference's
     # fitness of 48 of these very trees, 16 on the redo path
     sample = None
-    if (args.pop, args.cases, args.seed, args.min_depth, args.max_depth) == \
-            (65536, 2 ** 20, 2024, 4, 8) and not args.no_trig:
+    if args.full and (args.pop, args.cases, args.seed, args.min_depth,
+                      args.max_depth) == (65536, 2 ** 20, 2024, 4, 8) \
+            and not args.no_trig:
         torch.cuda.synchronize()
         spec = SymbRegMSE(X, y)          # finish() of the product path
         spec.n_cases = args.cases        # (all ranks' cases when sharded)
@@ -678,7 +720,7 @@ def main():
     # once per case into device columns (same values); reported beside the
     # headline, which evaluates every node of every tree like the reference
     leaves = None
-    if not args.no_trig and not args.no_trig_leaves:
+    if args.full and not args.no_trig and not args.no_trig_leaves:
         fl2 = Flattener(pset, trig_leaves=range(X.shape[0]))
         t0 = time.perf_counter()
         batch2 = fl2.flatten(pop)
@@ -700,7 +742,7 @@ def main():
     # cases evaluated in single precision (C++ f_eval<.., float>); reported
     # beside the fp64 headline with its tolerance
     fp32 = None
-    if not args.no_fp32 and not args.profile_only:
+    if args.full and not args.no_fp32 and not args.profile_only:
         ctx.set_trig_leaves(False)
         ctx.set_precision(_lib.GPE_PREC_F32)
         ctx.load_programs(batch)
@@ -716,10 +758,11 @@ def main():
         ctx.set_precision(_lib.GPE_PREC_F64)
 
     side = cold = deep = evolved = c3s = None
-    if dist is not None and not args.no_side_configs and not args.profile_only:
+    legs = args.full and not args.no_side_configs and not args.profile_only
+    if dist is not None and legs:
         progress("c3 population-sharded leg")
         c3s = c3_sharded_leg(local)
-    if world == 1 and not args.no_side_configs and not args.profile_only:
+    if world == 1 and legs:
         progress("side configs")
         side = side_configs()
         if not args.no_trig and args.pop == 65536 and args.cases == 2 ** 20:
@@ -799,7 +842,8 @@ def main():
             res["deep_core"] = deep
         if cold is not None:
             res["e2e"]["cold"] = cold
-        if world == 1 and not args.no_cpu_baseline and not args.profile_only:
+        if args.full and world == 1 and not args.no_cpu_baseline \
+                and not args.profile_only:
             progress("cpu baseline")
             res["cpu_baseline"] = cpu_baseline(pop, X_all, y, args.cpu_trees,
                                                args.cpu_cases)

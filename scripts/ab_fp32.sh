@@ -5,7 +5,7 @@ mkdir -p gpurun_out
 tag=$1; shift
 for spec in "$@"; do
   name=${spec%%:*}; lib=${spec#*:}
-  DEAP_AMD_LIB=$lib timeout -k 10 300 python3 -u bench.py --no-cpu-baseline --no-side-configs \
+  DEAP_AMD_LIB=$lib timeout -k 10 300 python3 -u bench.py --full --no-cpu-baseline --no-side-configs \
     --no-trig-leaves --steps 2 > gpurun_out/${tag}_${name}.log 2>&1 || exit 1
   python3 -c "
 import json

@@ -10,7 +10,7 @@ for spec in "$@"; do
     > gpurun_out/${tag}_${name}_probe.jsonl 2>&1 || exit 1
   echo "$name $(grep fit gpurun_out/${tag}_${name}_probe.jsonl | tr '\n' ' ')"
   if [ -z "${NO_BENCH:-}" ]; then
-    timeout -k 10 200 env $envs python3 -u bench.py --no-cpu-baseline --no-side-configs --no-fp32 \
+    timeout -k 10 200 env $envs python3 -u bench.py --full --no-cpu-baseline --no-side-configs --no-fp32 \
       --no-trig-leaves --steps 2 > gpurun_out/${tag}_${name}_bench.log 2>&1 || exit 1
     python3 -c "
 import json
