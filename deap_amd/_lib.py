@@ -62,6 +62,7 @@ SIGNATURES = {
     "gpe_last_timing": (_I, [_P, ctypes.POINTER(ctypes.c_float)]),
     "gpe_last_geometry": (_I, [_P, ctypes.POINTER(ctypes.c_int64)]),
     "gpe_last_geometry_ex": (_I, [_P, ctypes.POINTER(ctypes.c_int64), _I]),
+    "gpe_last_launch_shape": (_I, [_P, _I, ctypes.POINTER(ctypes.c_int64), _I]),
     "gpe_math_probe": (_I, [_P, _I, _P, _P, _I64]),
     "gpe_host_math": (_I, [_I, _P, _P, _I64]),
     "gpe_host_np_sum": (_I, [_P, _I64, _I64, _P]),
@@ -725,3 +726,18 @@ class Context(object):
                          "asm_typed", "asm_typed_P", "asm_typed_groups",
                          "typed_const"),
                         list(g)))
+
+    LAUNCHES = ("asm_fast", "asm_deep", "typed", "cpp_fast", "cpp_deep",
+                "fasm", "dasm")
+
+    def launch_shape(self, which):
+        """One launch of the last run as planned (gpe_last_launch_shape):
+        ``which`` is an index or one of ``LAUNCHES``."""
+        if isinstance(which, str):
+            which = self.LAUNCHES.index(which)
+        g = (ctypes.c_int64 * 12)()
+        self._check(self.lib.gpe_last_launch_shape(self.h, int(which), g, 12),
+                    "gpe_last_launch_shape")
+        return dict(zip(("programs", "P", "wpb", "waves", "n_slots", "K",
+                         "sdepth", "n_tiles", "tiles_per_group", "groups",
+                         "dbuf", "lds_bytes"), list(g)))

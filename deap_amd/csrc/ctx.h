@@ -21,6 +21,7 @@ struct Launch {
   int64_t programs = 0;
   int K = 0;                        // asm launches: the core's cases per lane
   bool dbuf = false;                // asm launches: two tile buffers (asm_dbuf)
+  size_t lds = 0;                   // dynamic LDS bytes its launch passed (0: not launched)
   char* h_pin = nullptr;            // pinned staging of the slot upload
   size_t h_pin_cap = 0;
 };

@@ -1334,6 +1334,11 @@ int run_common(gpe_ctx* ctx, int mode, double* hi, double* lo,
                          ctx->prec == GPE_PREC_F64 &&
                          (ctx->fasm.n_slots || ctx->dasm.n_slots);
   ctx->last_exact_all = exact_all;
+  // (cleared before the exact cores run: run_exact_asm counts the pairs it
+  // leaves to the C++ pair pass in redo_exact_cpp)
+  ctx->redo_programs = 0;
+  ctx->redo_tiles = 0;
+  ctx->redo_exact_cpp = 0;
   if (exact_all) {
     std::vector<int32_t> rx, rxd, rest;
     for (int64_t i = 0; i < ctx->fasm.n_slots; ++i)
@@ -1370,9 +1375,6 @@ int run_common(gpe_ctx* ctx, int mode, double* hi, double* lo,
   if ((rc = launch_reduce(ctx, ctx->fast, hi, lo))) return rc;
   if ((rc = launch_reduce(ctx, ctx->deep, hi, lo))) return rc;
   HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
-  ctx->redo_programs = 0;
-  ctx->redo_tiles = 0;
-  ctx->redo_exact_cpp = 0;
   // the redo bookkeeping rides the same stream as the main pass: (sharded)
   // the flags' all-reduce, the flagged programs compacted on the device in
   // program order, and ONE pinned D2H of [flagged tiles, flagged programs,
@@ -3306,6 +3308,27 @@ int gpe_last_geometry_ex(const gpe_ctx* ctx, int64_t* o, int n) {
   g[15] = ctx->tasm.groups;
   g[16] = ctx->planned_mode == GPE_MODE_HITS_BOOL ? ctx->n_kc : 0;   // constants: no core run
   std::copy(g, g + std::min(n, GPE_GEOMETRY_FIELDS), o);
+  return 0;
+}
+
+int gpe_last_launch_shape(const gpe_ctx* ctx, int which, int64_t* o, int n) {
+  if (!ctx || !o || n < 0) return GPE_E_INVALID;
+  const bool x = ctx->last_exact_all;
+  const Launch* L = nullptr;
+  switch (which) {
+    case GPE_LAUNCH_ASM_FAST: L = x ? &ctx->redo_xasm : &ctx->fasm; break;
+    case GPE_LAUNCH_ASM_DEEP: L = x ? &ctx->redo_xasm_deep : &ctx->dasm; break;
+    case GPE_LAUNCH_TYPED: L = &ctx->tasm; break;
+    case GPE_LAUNCH_CPP_FAST: L = &ctx->fast; break;
+    case GPE_LAUNCH_CPP_DEEP: L = &ctx->deep; break;
+    case GPE_LAUNCH_FASM: L = &ctx->fasm; break;
+    case GPE_LAUNCH_DASM: L = &ctx->dasm; break;
+    default: return GPE_E_INVALID;
+  }
+  const int64_t g[GPE_LAUNCH_SHAPE_FIELDS] = {
+      L->programs, L->P, L->wpb, L->waves, L->n_slots, L->K, L->sdepth, L->n_tiles,
+      L->tiles_per_group, L->groups, L->dbuf ? 1 : 0, (int64_t)L->lds};
+  std::copy(g, g + std::min(n, GPE_LAUNCH_SHAPE_FIELDS), o);
   return 0;
 }
 

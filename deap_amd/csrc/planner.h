@@ -79,6 +79,7 @@ int plan(gpe_ctx* ctx, Launch& L, const std::vector<int32_t>& progs, bool deep,
   L.waves = 0;
   L.programs = (int64_t)progs.size();
   L.sdepth = 1;
+  L.lds = 0;
   L.K = is_asm ? asm_core_k(ctx, deep_core, exact, typed) : 0;
   if (progs.empty()) {
     L.slot_prog.clear();         // (no stale slots of an earlier batch)
@@ -334,6 +335,7 @@ int launch_f(gpe_ctx* ctx, Launch& L, bool deep, unsigned long long* err,
     a.gtab_lds = 1;
     lds += kGlibcLdsDoubles * sizeof(double);
   }
+  L.lds = lds;
   auto kern = f_eval<K, D, MODE, R, EXACT>;
   HIPCHK(hipFuncSetAttribute((const void*)kern,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -379,6 +381,7 @@ int launch_asm(gpe_ctx* ctx, Launch& L, unsigned long long* err,
   }
   a.dbuf = L.dbuf ? 1 : 0;
   const size_t lds = lds_bytes_asm(ctx, L.P, L.wpb, L.K, L.dbuf, exact);
+  L.lds = lds;
   const bool f32 = ctx->prec == GPE_PREC_F32;
   auto kern = exact ? (deep_core ? f_eval_asm<false, true, true> : f_eval_asm<false, false, true>)
               : deep_core ? (f32 ? f_eval_asm<true, true> : f_eval_asm<false, true>)
@@ -408,6 +411,7 @@ int launch_asm_typed(gpe_ctx* ctx, Launch& L) {
   a.tiles_per_group = L.tiles_per_group;
   a.part = L.d_part;
   const size_t lds = lds_bytes_typed(ctx);
+  L.lds = lds;
   HIPCHK(hipFuncSetAttribute((const void*)f_eval_asm_typed,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   dim3 grid((unsigned)L.groups, (unsigned)(L.waves / L.wpb));
@@ -436,6 +440,7 @@ int launch_b(gpe_ctx* ctx, Launch& L, bool deep) {
   a.tiles_per_group = L.tiles_per_group;
   a.part = L.d_part;
   const size_t lds = lds_bytes(ctx, deep);
+  L.lds = lds;
   dim3 grid((unsigned)L.groups, (unsigned)(L.waves / kWaves));
   if (G) {                                   // tiny case sets: lane-packed
     auto kern = b_eval_lanes<D>;

@@ -372,6 +372,28 @@ int gpe_last_geometry(const gpe_ctx* ctx, int64_t* out8);
 #define GPE_GEOMETRY_FIELDS 17
 int gpe_last_geometry_ex(const gpe_ctx* ctx, int64_t* out, int n);
 
+/* One launch of the last gpe_run as the planner shaped it (read-only, for
+ * tests and reports).  `which`: the D = 5 asm core and the deep asm core as
+ * they ran (the exact cores' launches when the run put its asm programs on
+ * them, as gpe_last_geometry reports them, else the table or fp32 cores'),
+ * the typed core, the C++ fast and deep kernels, and the table / fp32 asm
+ * cores' own plans (from which an exact run takes its programs).  Fields:
+ * programs, programs per wave, waves per block, waves, slots (waves x
+ * programs per wave, -1 padded), cases per lane of an asm core (0: a C++
+ * kernel), stack slots, case tiles, tiles per group, tile groups, two tile
+ * buffers (0 / 1), and the dynamic LDS bytes the launch passed to its kernel
+ * (0: planned but not launched, or no programs).  Writes the first
+ * min(n, GPE_LAUNCH_SHAPE_FIELDS) fields; GPE_E_INVALID for another `which`. */
+#define GPE_LAUNCH_ASM_FAST 0
+#define GPE_LAUNCH_ASM_DEEP 1
+#define GPE_LAUNCH_TYPED 2
+#define GPE_LAUNCH_CPP_FAST 3
+#define GPE_LAUNCH_CPP_DEEP 4
+#define GPE_LAUNCH_FASM 5
+#define GPE_LAUNCH_DASM 6
+#define GPE_LAUNCH_SHAPE_FIELDS 12
+int gpe_last_launch_shape(const gpe_ctx* ctx, int which, int64_t* out, int n);
+
 /* Diagnostic (host only): the program -> threaded-code translation the asm
  * core executes, with a caller-given handler table; starts[i] = -1 for
  * programs the asm core does not run.  Lets CPU tests check translation and
