@@ -68,6 +68,10 @@ SIGNATURES = {
     "gpe_host_np_sum": (_I, [_P, _I64, _I64, _P]),
     "gpe_debug_translate": (_I, [_P, _I64, _P, _I64, _P, _I, _P, _I, _P,
                                  _I64, _P, _P]),
+    "gpe_debug_translate_ranges": (_I, [_P, _I64, _P, _I64, _P, _I, _P, _I, _P,
+                                        _I64, _P, _P, _P, _P]),
+    "gpe_debug_trig_classes": (_I, [_P, _I64, _P, _P, _I, _P, _I64]),
+    "gpe_last_trig_classes": (_I, [_P, ctypes.POINTER(ctypes.c_int64)]),
     "gpe_comm_unique_id": (_I, [_P]),
     "gpe_comm_init": (_I, [_P, _I, _I, _P]),
     "gpe_comm_info": (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
@@ -159,21 +163,49 @@ def host_np_sum(rows):
     return out
 
 
-def debug_translate(batch, nv, table):
-    """Host-only: threaded code the asm core would run (see header)."""
+TRIG_CLASSES = ("general", "mid", "small")
+
+
+def debug_trig_classes(words, lo, hi):
+    """Host-only: the range pass (csrc/trig_ranges.h) over one program's
+    flattener words with column bounds lo[v], hi[v]: the class index
+    (``TRIG_CLASSES``) of each sin/cos node, in word order."""
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    lo = np.ascontiguousarray(lo, dtype=np.float64)
+    hi = np.ascontiguousarray(hi, dtype=np.float64)
+    assert lo.shape == hi.shape and lo.ndim == 1
+    out = np.zeros(max(len(words), 1), dtype=np.int32)
+    n = load().gpe_debug_trig_classes(_ptr(words), len(words), _ptr(lo), _ptr(hi),
+                                      len(lo), _ptr(out), len(out))
+    if n < 0:
+        raise GpeError("gpe_debug_trig_classes: malformed program")
+    return out[:n]
+
+
+def debug_translate(batch, nv, table, bounds=None):
+    """Host-only: threaded code the asm core would run (see header).
+    ``bounds`` = (lo, hi) per column: the exact cores' translation, sin/cos
+    words by proven range (gpe_debug_translate_ranges)."""
     lib = load()
     code = np.ascontiguousarray(batch.code, dtype=np.uint32)
     off = np.ascontiguousarray(batch.offsets, dtype=np.int64)
     depth = np.ascontiguousarray(batch.depth, dtype=np.int32)
     table = np.ascontiguousarray(table, dtype=np.uint32)
-    cap = 3 * len(code) + 16
+    # (every program starts on a 16-word window)
+    cap = 3 * len(code) + 16 * (len(depth) + 1)
     out = np.zeros(cap, dtype=np.uint32)
     starts = np.zeros(len(depth), dtype=np.int64)
     n_out = ctypes.c_int64()
-    rc = lib.gpe_debug_translate(_ptr(code), len(code), _ptr(off), len(depth),
-                                 _ptr(depth), int(nv), _ptr(table),
-                                 len(table), _ptr(out), cap, _ptr(starts),
-                                 ctypes.byref(n_out))
+    lo = hi = None
+    if bounds is not None:
+        lo = np.ascontiguousarray(bounds[0], dtype=np.float64)
+        hi = np.ascontiguousarray(bounds[1], dtype=np.float64)
+        assert len(lo) == len(hi) == int(nv)
+    rc = lib.gpe_debug_translate_ranges(
+        _ptr(code), len(code), _ptr(off), len(depth), _ptr(depth), int(nv),
+        _ptr(table), len(table), _ptr(out), cap, _ptr(starts),
+        ctypes.byref(n_out), None if lo is None else _ptr(lo),
+        None if hi is None else _ptr(hi))
     if rc != 0:
         raise GpeError("gpe_debug_translate failed (%d)" % rc)
     return out[:n_out.value], starts
@@ -729,6 +761,14 @@ class Context(object):
 
     LAUNCHES = ("asm_fast", "asm_deep", "typed", "cpp_fast", "cpp_deep",
                 "fasm", "dasm")
+
+    def trig_classes(self):
+        """sin/cos words of the last exact-core translation per class
+        (gpe_last_trig_classes): {"general", "mid", "small"}."""
+        g = (ctypes.c_int64 * 3)()
+        self._check(self.lib.gpe_last_trig_classes(self.h, g),
+                    "gpe_last_trig_classes")
+        return dict(zip(TRIG_CLASSES, (int(v) for v in g)))
 
     def launch_shape(self, which):
         """One launch of the last run as planned (gpe_last_launch_shape):

@@ -100,7 +100,7 @@ int run_exact_asm(gpe_ctx* ctx, const std::vector<int32_t>& rx, double* hi,
   T.tab[1] = ctx->d_jump_asm_exact_deep;
   T.ids[1] = kIdsExactDeep;
   int rc0 = translate_device(ctx, &cls, T, false, false, &ctx->d_acode_x, &ctx->acode_x_cap,
-                             &ctx->d_astart_x, &ctx->astart_x_cap);
+                             &ctx->d_astart_x, &ctx->astart_x_cap, true);
   if (rc0) return rc0;
   if (ensure(ctx, &ctx->d_redo2, &ctx->redo2_cap, (size_t)n_prog)) return GPE_E_HIP;
   HIPCHK(hipMemsetAsync(ctx->d_redo2, 0, (size_t)n_prog * sizeof(uint32_t), ctx->stream));

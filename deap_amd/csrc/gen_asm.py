@@ -300,7 +300,7 @@ class Gen(object):
         self.vmax = max(self.vmax, hi + 1)
 
     # --------------------------------------------------------- dispatch --
-    def dispatch_head(self, nconst=0):
+    def dispatch_head(self, nconst=0, alias_entry=None):
         """Read the inline constant (if any) and the next word from the
         window and advance M0.  A program word is the low half of its
         handler's absolute address (the host adds the kernel's base, probed
@@ -313,6 +313,8 @@ class Gen(object):
             self.e("s_movrels_b32 s%d, s%d" % (self.CA, W))
             self.e("s_movrels_b32 s%d, s%d" % (self.CA + 1, W + 1))
         self.e("s_movrels_b32 s%d, s%d" % (self.TGT, W + nconst))
+        if alias_entry:                  # (range_handlers' aliases join here)
+            self.label(alias_entry)
         self.e("s_add_u32 m0, m0, %d" % (nconst + 1))
 
     def prologue_base(self):
@@ -1398,7 +1400,7 @@ class Gen(object):
         both("v_mov_b32_e32 {x_lo}, {r_lo}", [], ["r"])
         return seq
 
-    def glibc_seq4(self, want):
+    def glibc_seq4(self, want, rng=None):
         """glibc 2.35 __sin/__cos (gpeval.hip glibc_trig_t) for the K = 2
         chains, every rounding of glibc_seq3's, in fewer VALU instructions
         (round 6; the handler is VALU-issue bound, and every VALU instruction
@@ -1429,9 +1431,28 @@ class Gen(object):
           fma's of the correction are one instruction stream for both.
         SGPRs: CA / BASE the chains' do_cos masks, SMASK the handler's EXEC,
         s80 the sign mask (the slow path: s[80:81] a mask pair), s101 the
-        slow path's copy of s81."""
+        slow path's copy of s81.
+
+        rng: the range-specialised handlers (trig_ranges.h proves every
+        lane's argument, pad lanes included, inside the range before the
+        translator emits their words).  The operations a lane of that range
+        runs in the general handler, in the same order, without the tests
+        that find the range: no |x|.hi, no VRED update, no 2.426265 or
+        105414350 compare, no reduce_sincos or __branred block.
+        "mid" (|x| < 2.42): M[k] = |x| < 0.85546875 by one fp64 compare of
+        |x| with the double whose high word is 0x3feb6000 (low word 0: the
+        same lanes as the u32 test of |x|.hi), d = the handler's other lanes;
+        sin: n = x.hi for all lanes (the result's sign is x's in both
+        ranges), so the do_sin lanes' sign fold goes.  "small"
+        (|x| < 0.855): no compare, no d block; sin: do_sin(x, 0) for every
+        lane (n = x.hi), cos: do_cos(x, 0) for every lane — no do_sin lanes,
+        no TAYLOR_SIN, no sign (n = 0).  da = 0 and its sign fold, and the
+        do_cos lanes' xr + da, stay: their removal is not an identity for
+        every signed zero by construction, and they are cheap."""
         assert self.K == 2 and GLIBC4
+        assert rng in (None, "mid", "small") and (rng is None or self.salu)
         cos = want == "cos"
+        mid, small = rng == "mid", rng == "small"
         seq = []
         M = [self.sp(self.CA), self.sp(self.BASE)]
         SV = self.sp(self.SMASK)
@@ -1445,7 +1466,7 @@ class Gen(object):
         SK = self.SCONST if self.m0lane else SSAVE
         assert not (self.prefetch and not self.m0lane)
         S = GLIBC_SPLIT_S
-        W = "%s_%%=" % want
+        W = "%s_%%=" % (want + ("_" + rng if rng else ""))
         N = ["{nn_lo}", "{nn_hi}"]
 
         def const(name):
@@ -1473,7 +1494,8 @@ class Gen(object):
                   [pfx + "y", "x", "da"])
                 a(k, "v_add_f64 {da}, {da}, @HP1@", ["da"], ["da"])
             else:
-                a(k, "v_mov_b32_e32 %s, {x_hi}" % N[k], ["nn"], ["x", "nn"])
+                if not rng:              # (mid: set for all lanes before)
+                    a(k, "v_mov_b32_e32 %s, {x_hi}" % N[k], ["nn"], ["x", "nn"])
                 a(k, "v_add_f64 {x}, @HP0@, -|{x}|", [], ["x"])
                 a(k, "v_mov_b64_e32 {da}, @HP1@", ["da"], ["da"])
 
@@ -1508,133 +1530,170 @@ class Gen(object):
             a(k, "v_cmp_neq_f32_e64 vcc, 0, %s\ns_or_b64 %s, %s, vcc"
               % (N[k], M[k], M[k]), [], ["nn"])
 
-        # ---- |x|.hi (VRED: its running max); M[k] = |x| < 0.855469; the
-        # slow-path test; (a, da, n) = (x, 0, 0)
-        if not self.salu:
-            a(0, "s_mov_b64 %s, exec" % SV)
-        if os.environ.get("GEN_ASM_EXPERIMENT") == "dup_salu":
-            # (pricing: six more wave-uniform SALU per call, no dependences)
-            a(0, "\n".join(["s_mov_b64 %s, exec" % SV] * 6))
-        both("v_and_b32_e32 {hx}, 0x7fffffff, {x_hi}", ["hx"], ["x"])
-        a(1, "v_max3_u32 v%d, v%d, {hx@0}, {hx}" % (self.VRED, self.VRED),
-          [], ["hx@0", "hx"])
-        if self.m0lane:
-            # the compares straight into their mask pairs (VOP3: the
-            # threshold from an SGPR), chain 1's 2.426265 test early (SP)
-            if self.salu:                    # (set by the core's prologue)
-                assert self.SPF == SSAVE
-                for k in range(2):
-                    a(k, "v_cmp_gt_u32_e64 %s, s%d, {hx}" % (M[k], SSAVE), [], ["hx"])
+        def ranges_general():
+            # ---- |x|.hi (VRED: its running max); M[k] = |x| < 0.855469; the
+            # slow-path test; (a, da, n) = (x, 0, 0)
+            if not self.salu:
+                a(0, "s_mov_b64 %s, exec" % SV)
+            if os.environ.get("GEN_ASM_EXPERIMENT") == "dup_salu":
+                # (pricing: six more wave-uniform SALU per call, no dependences)
+                a(0, "\n".join(["s_mov_b64 %s, exec" % SV] * 6))
+            both("v_and_b32_e32 {hx}, 0x7fffffff, {x_hi}", ["hx"], ["x"])
+            a(1, "v_max3_u32 v%d, v%d, {hx@0}, {hx}" % (self.VRED, self.VRED),
+              [], ["hx@0", "hx"])
+            if self.m0lane:
+                # the compares straight into their mask pairs (VOP3: the
+                # threshold from an SGPR), chain 1's 2.426265 test early (SP)
+                if self.salu:                    # (set by the core's prologue)
+                    assert self.SPF == SSAVE
+                    for k in range(2):
+                        a(k, "v_cmp_gt_u32_e64 %s, s%d, {hx}" % (M[k], SSAVE), [], ["hx"])
+                else:
+                    a(0, "s_mov_b32 s%d, 0x%x" % (SK, GLIBC_T0855))
+                    for k in range(2):
+                        a(k, "v_cmp_gt_u32_e64 %s, s%d, {hx}" % (M[k], SK), [], ["hx"])
+                a(1, "s_mov_b32 s%d, 0x400368fd\n"
+                     "v_cmp_gt_u32_e64 %s, s%d, {hx}" % (SK, SP, SK), [], ["hx"])
             else:
-                a(0, "s_mov_b32 s%d, 0x%x" % (SK, GLIBC_T0855))
                 for k in range(2):
-                    a(k, "v_cmp_gt_u32_e64 %s, s%d, {hx}" % (M[k], SK), [], ["hx"])
-            a(1, "s_mov_b32 s%d, 0x400368fd\n"
-                 "v_cmp_gt_u32_e64 %s, s%d, {hx}" % (SK, SP, SK), [], ["hx"])
-        else:
+                    a(k, "v_cmp_gt_u32_e32 vcc, 0x3feb6000, {hx}\ns_mov_b64 %s, vcc"
+                      % M[k], [], ["hx"])
+            a(1, "v_cmp_lt_u32_e32 vcc, 0x%x, v%d" % (BRANRED_HI - 1, self.VRED))
+            both("v_mov_b64_e32 {da}, 0", ["da"], [])
+            a(0, "v_mov_b64_e32 {nn}, 0", ["nn"], [])
+            a(1, "s_cbranch_vccnz .Lslow_%s" % W)
+            # ---- fast path (no lane at or past 105414350): per chain, d = lanes
+            # below 2.426265 and not small, e = the rest
             for k in range(2):
-                a(k, "v_cmp_gt_u32_e32 vcc, 0x3feb6000, {hx}\ns_mov_b64 %s, vcc"
-                  % M[k], [], ["hx"])
-        a(1, "v_cmp_lt_u32_e32 vcc, 0x%x, v%d" % (BRANRED_HI - 1, self.VRED))
-        both("v_mov_b64_e32 {da}, 0", ["da"], [])
-        a(0, "v_mov_b64_e32 {nn}, 0", ["nn"], [])
-        a(1, "s_cbranch_vccnz .Lslow_%s" % W)
-        # ---- fast path (no lane at or past 105414350): per chain, d = lanes
-        # below 2.426265 and not small, e = the rest
-        for k in range(2):
-            lab = "_%d_%s" % (k, W)
-            if self.m0lane and k == 1:           # (its test is in SP already)
-                a(k, "s_andn2_b64 exec, %s, %s\n"
-                     "s_andn2_b64 vcc, %s, %s\n%s"
-                     "s_cbranch_execz .Lfd%s" % (SP, M[k], SV, SP, "" if cos else
-                                                 "s_mov_b64 %s, exec\n" % M[k], lab))
+                lab = "_%d_%s" % (k, W)
+                if self.m0lane and k == 1:           # (its test is in SP already)
+                    a(k, "s_andn2_b64 exec, %s, %s\n"
+                         "s_andn2_b64 vcc, %s, %s\n%s"
+                         "s_cbranch_execz .Lfd%s" % (SP, M[k], SV, SP, "" if cos else
+                                                     "s_mov_b64 %s, exec\n" % M[k], lab))
+                else:
+                    a(k, "v_cmp_gt_u32_e32 vcc, 0x400368fd, {hx}\n"
+                         "s_andn2_b64 exec, vcc, %s\n"
+                         "s_andn2_b64 vcc, %s, vcc\n%s"
+                         "s_cbranch_execz .Lfd%s" % (M[k], SV, "" if cos else
+                                                     "s_mov_b64 %s, exec\n" % M[k], lab),
+                      [], ["hx"])
+                dblock(k, "")
+                if self.salu:
+                    # (SCC: vcc != 0, from the s_andn2 that formed vcc; the d
+                    # block is VALU only)
+                    a(k, ".Lfd%s:\ns_cbranch_scc1 .Leo%s" % (lab, lab))
+                    a(k, "<OOL>\n.Leo%s:\ns_mov_b64 exec, vcc" % lab)
+                    eblock(k, "")
+                    a(k, "s_branch .Lfe%s\n<MAIN>" % lab)
+                elif OOL:
+                    # reduce_sincos lanes are rare (17 % of chain-calls): the
+                    # block sits out of line, the common path falls through
+                    a(k, ".Lfd%s:\ns_mov_b64 exec, vcc\ns_cbranch_execnz .Leo%s" % (lab, lab))
+                    a(k, "<OOL>\n.Leo%s:" % lab)
+                    eblock(k, "")
+                    a(k, "s_branch .Lfe%s\n<MAIN>" % lab)
+                else:
+                    a(k, ".Lfd%s:\ns_mov_b64 exec, vcc\ns_cbranch_execz .Lfe%s" % (lab, lab))
+                    eblock(k, "")
+                # (the next chain's compares run under the handler's EXEC;
+                # with salu, chain 1's first op sets EXEC from its masks)
+                if self.salu and k == 0:
+                    a(k, ".Lfe%s:" % lab)
+                else:
+                    a(k, ".Lfe%s:\ns_mov_b64 exec, %s" % (lab, SV))
+            if OOL:
+                a(1, "<OOL>")
             else:
+                a(1, "s_branch .Ljoin_%s" % W)
+            # ---- slow path: the three ranges tested per chain, __branred for the
+            # finite lanes at or past 105414350 (its constants loaded once)
+            a(1, ".Lslow_%s:" % W if self.m0lane else
+              ".Lslow_%s:\ns_mov_b32 s%d, s%d" % (W, SSAVE, self.SM0))
+            keep = {"x", "da", "n", "BK", "bz", "bmp2"}
+
+            def brops(k):
+                """__branred's ops for chain k: its temporaries renamed (no live
+                range shared with the blocks above), n as the chain's half of
+                the nn pair, s[80:81] its select pair."""
+                out = []
+                ren = lambda v: "nn" if v == "n" else v if v in keep else "z" + v
+                for t, d, u, _ in self.branred_ops(k, want, (self.SCONST, self.SM0)):
+                    for v in set(d) | set(u):
+                        if v not in keep:
+                            for sfx in ("", "_lo", "_hi"):
+                                t = t.replace("{%s%s}" % (v, sfx), "{z%s%s}" % (v, sfx))
+                    t = t.replace("{n}", N[k])
+                    out.append((t, [ren(v) for v in d], [ren(v) for v in u]))
+                return out
+            for t, d, u in brops(0)[:4]:          # bz, BK, bmp2 (shared), waited
+                a(1, t, d, u)
+            for k in range(2):
+                lab = "_%d_%s" % (k, W)
                 a(k, "v_cmp_gt_u32_e32 vcc, 0x400368fd, {hx}\n"
                      "s_andn2_b64 exec, vcc, %s\n"
-                     "s_andn2_b64 vcc, %s, vcc\n%s"
-                     "s_cbranch_execz .Lfd%s" % (M[k], SV, "" if cos else
+                     "s_mov_b64 %s, vcc\n%s"
+                     "s_cbranch_execz .Lsd%s" % (M[k], SP, "" if cos else
                                                  "s_mov_b64 %s, exec\n" % M[k], lab),
                   [], ["hx"])
-            dblock(k, "")
-            if self.salu:
-                # (SCC: vcc != 0, from the s_andn2 that formed vcc; the d
-                # block is VALU only)
-                a(k, ".Lfd%s:\ns_cbranch_scc1 .Leo%s" % (lab, lab))
-                a(k, "<OOL>\n.Leo%s:\ns_mov_b64 exec, vcc" % lab)
-                eblock(k, "")
-                a(k, "s_branch .Lfe%s\n<MAIN>" % lab)
-            elif OOL:
-                # reduce_sincos lanes are rare (17 % of chain-calls): the
-                # block sits out of line, the common path falls through
-                a(k, ".Lfd%s:\ns_mov_b64 exec, vcc\ns_cbranch_execnz .Leo%s" % (lab, lab))
-                a(k, "<OOL>\n.Leo%s:" % lab)
-                eblock(k, "")
-                a(k, "s_branch .Lfe%s\n<MAIN>" % lab)
+                dblock(k, "s")
+                a(k, ".Lsd%s:\ns_mov_b64 exec, %s\n"
+                     "v_cmp_gt_u32_e32 vcc, 0x%x, {hx}\n"
+                     "s_andn2_b64 exec, vcc, %s\n"
+                     "s_mov_b64 %s, vcc\n"
+                     "s_cbranch_execz .Lse%s" % (lab, SV, BRANRED_HI, SP, SP, lab),
+                  [], ["hx"])
+                eblock(k, "s")
+                a(k, ".Lse%s:\ns_mov_b64 exec, %s\n"
+                     "v_cmp_gt_u32_e32 vcc, 0x7ff00000, {hx}\n"
+                     "s_andn2_b64 exec, vcc, %s\n"
+                     "s_cbranch_execz .Lsr%s" % (lab, SV, SP, lab), [], ["hx"])
+                for t, d, u in brops(k)[4:]:
+                    a(k, t, d, u)
+                a(k, "v_cmp_neq_f32_e64 vcc, 0, %s\ns_or_b64 %s, %s, vcc"
+                  % (N[k], M[k], M[k]), [], ["nn"])
+                a(k, ".Lsr%s:\ns_mov_b64 exec, %s" % (lab, SV))
+            restore = "" if self.m0lane else "s_mov_b32 s%d, s%d\n" % (self.SM0, SSAVE)
+            if OOL:
+                a(1, "%ss_branch .Ljoin_%s\n<MAIN>\n.Ljoin_%s:" % (restore, W, W))
             else:
-                a(k, ".Lfd%s:\ns_mov_b64 exec, vcc\ns_cbranch_execz .Lfe%s" % (lab, lab))
-                eblock(k, "")
-            # (the next chain's compares run under the handler's EXEC;
-            # with salu, chain 1's first op sets EXEC from its masks)
-            if self.salu and k == 0:
-                a(k, ".Lfe%s:" % lab)
-            else:
-                a(k, ".Lfe%s:\ns_mov_b64 exec, %s" % (lab, SV))
-        if OOL:
-            a(1, "<OOL>")
-        else:
-            a(1, "s_branch .Ljoin_%s" % W)
-        # ---- slow path: the three ranges tested per chain, __branred for the
-        # finite lanes at or past 105414350 (its constants loaded once)
-        a(1, ".Lslow_%s:" % W if self.m0lane else
-          ".Lslow_%s:\ns_mov_b32 s%d, s%d" % (W, SSAVE, self.SM0))
-        keep = {"x", "da", "n", "BK", "bz", "bmp2"}
+                a(1, "%s.Ljoin_%s:" % (restore, W))
 
-        def brops(k):
-            """__branred's ops for chain k: its temporaries renamed (no live
-            range shared with the blocks above), n as the chain's half of
-            the nn pair, s[80:81] its select pair."""
-            out = []
-            ren = lambda v: "nn" if v == "n" else v if v in keep else "z" + v
-            for t, d, u, _ in self.branred_ops(k, want, (self.SCONST, self.SM0)):
-                for v in set(d) | set(u):
-                    if v not in keep:
-                        for sfx in ("", "_lo", "_hi"):
-                            t = t.replace("{%s%s}" % (v, sfx), "{z%s%s}" % (v, sfx))
-                t = t.replace("{n}", N[k])
-                out.append((t, [ren(v) for v in d], [ren(v) for v in u]))
-            return out
-        for t, d, u in brops(0)[:4]:          # bz, BK, bmp2 (shared), waited
-            a(1, t, d, u)
-        for k in range(2):
-            lab = "_%d_%s" % (k, W)
-            a(k, "v_cmp_gt_u32_e32 vcc, 0x400368fd, {hx}\n"
-                 "s_andn2_b64 exec, vcc, %s\n"
-                 "s_mov_b64 %s, vcc\n%s"
-                 "s_cbranch_execz .Lsd%s" % (M[k], SP, "" if cos else
-                                             "s_mov_b64 %s, exec\n" % M[k], lab),
-              [], ["hx"])
-            dblock(k, "s")
-            a(k, ".Lsd%s:\ns_mov_b64 exec, %s\n"
-                 "v_cmp_gt_u32_e32 vcc, 0x%x, {hx}\n"
-                 "s_andn2_b64 exec, vcc, %s\n"
-                 "s_mov_b64 %s, vcc\n"
-                 "s_cbranch_execz .Lse%s" % (lab, SV, BRANRED_HI, SP, SP, lab),
-              [], ["hx"])
-            eblock(k, "s")
-            a(k, ".Lse%s:\ns_mov_b64 exec, %s\n"
-                 "v_cmp_gt_u32_e32 vcc, 0x7ff00000, {hx}\n"
-                 "s_andn2_b64 exec, vcc, %s\n"
-                 "s_cbranch_execz .Lsr%s" % (lab, SV, SP, lab), [], ["hx"])
-            for t, d, u in brops(k)[4:]:
-                a(k, t, d, u)
-            a(k, "v_cmp_neq_f32_e64 vcc, 0, %s\ns_or_b64 %s, %s, vcc"
-              % (N[k], M[k], M[k]), [], ["nn"])
-            a(k, ".Lsr%s:\ns_mov_b64 exec, %s" % (lab, SV))
-        restore = "" if self.m0lane else "s_mov_b32 s%d, s%d\n" % (self.SM0, SSAVE)
-        if OOL:
-            a(1, "%ss_branch .Ljoin_%s\n<MAIN>\n.Ljoin_%s:" % (restore, W, W))
+
+        def ranges_known():
+            """rng: the masks and (a, da, n) with the range proven."""
+            if not (cos and small):
+                # n = x.hi (sin: the result's sign; all lanes, before the d
+                # block replaces x); cos mid: n = 0 (the do_sin lanes fold
+                # a's sign in)
+                if cos:
+                    a(0, "v_mov_b64_e32 {nn}, 0", ["nn"], [])
+                else:
+                    for k in range(2):
+                        a(k, "v_mov_b32_e32 %s, {x_hi}" % N[k], ["nn"],
+                          ["x"] + (["nn"] if k else []))
+            both("v_mov_b64_e32 {da}, 0", ["da"], [])
+            if small:
+                return
+            # 0.85546875 as a double (0x3feb6000 : 0) in the free pair SP
+            a(0, "s_mov_b32 %s, 0\ns_mov_b32 s%d, s%d" % (SC, self.SM0, SSAVE))
+            for k in range(2):
+                a(k, "v_cmp_gt_f64_e64 %s, %s, |{x}|" % (M[k], SP), [], ["x"])
+            for k in range(2):
+                lab = ".Lmd%d_%s" % (k, W)
+                # d = the handler's lanes that are not small (sin: the do_cos
+                # lanes; cos: the small ones are)
+                a(k, "s_andn2_b64 exec, %s, %s\n%s"
+                     "s_cbranch_execz %s" % (SV, M[k], "" if cos else
+                                             "s_mov_b64 %s, exec\n" % M[k], lab))
+                dblock(k, "")
+                a(k, lab + ":")
+            a(1, "s_mov_b64 exec, %s" % SV)
+
+        if rng:
+            ranges_known()
         else:
-            a(1, "%s.Ljoin_%s:" % (restore, W))
+            ranges_general()
 
         # ---- do_sincos(a, da, n): M[k] = the chain's do_cos lanes.  dx
         # signed as do_sin / do_cos sign it (a < 0: -dx), in place: the
@@ -1650,14 +1709,18 @@ class Gen(object):
         both("v_add_f64 {xr}, |{x}|, -{q1}", ["xr"], ["x", "q1"])
         # do_cos lanes: entries B[i], NA[i]; v = xr + dx (into xr), dx := v
         # (s = v + v xx p)
-        for k in range(2):
+        # (small: sin has no do_cos lanes; cos has no others, EXEC stays)
+        for k in range(0 if small and not cos else 2):
             lab = ".Lbc%d_%s" % (k, W)
-            a(k, "s_mov_b64 exec, %s\ns_cbranch_execz %s" % (M[k], lab))
+            if not small:
+                a(k, "s_mov_b64 exec, %s\ns_cbranch_execz %s" % (M[k], lab))
             a(k, "v_add_u32_e32 {adr0}, 0x%x, {adr0}" % S, ["adr0"], ["adr0"])
             a(k, "v_add_f64 {xr}, {xr}, {da}", ["xr"], ["xr", "da"])
             a(k, "v_mov_b64_e32 {da}, {xr}", ["da"], ["xr", "da"])
-            a(k, lab + ":")
-        a(1, "s_mov_b64 exec, %s" % SV)
+            if not small:
+                a(k, lab + ":")
+        if not small:
+            a(1, "s_mov_b64 exec, %s" % SV)
         both("v_mul_f64 {xx}, {xr}, {xr}", ["xx"], ["xr"])
         both("v_mul_f64 {m}, {xr}, {xx}", ["m"], ["xr", "xx"])
         both("v_fma_f64 {p}, {xx}, @SN5@, @SN3@", ["p"], ["xx"])
@@ -1679,9 +1742,14 @@ class Gen(object):
         # result is for (the handler's, less those).  glibc's |x| < 2^-26
         # (sin: x) needs no case of its own: TAYLOR_SIN(x x, |x|, 0) is |x|
         # exactly there (|x|^3 / 6 is below half an ulp; +0 for +-0)
-        for k in range(2):
+        # (small: cos has no do_sin lanes; sin has no others, EXEC is the
+        # handler's.  rng sin: n = x.hi already, no fold)
+        for k in range(0 if small and cos else 2):
             lab = ".Lbs%d_%s" % (k, W)
-            if self.salu:
+            if small:
+                if k:                    # (chain 0's 0.126 compare narrowed it)
+                    a(k, "s_mov_b64 exec, %s" % SV)
+            elif self.salu:
                 # (no do_sin lanes — rare: M := SV out of line; the 0.126
                 # compare writes EXEC itself)
                 a(k, "s_andn2_b64 exec, %s, %s\ns_cbranch_scc0 .Lns%d_%s"
@@ -1693,8 +1761,9 @@ class Gen(object):
                   % (SV, M[k], M[k], SV, lab))
             a(k, "v_add_f64 {s}, {s}, {xr}", ["s"], ["s", "xr"])
             a(k, "v_fma_f64 {w}, {da}, {xr}, {w}", ["w"], ["da", "xr", "w"])
-            a(k, "v_bitop3_b32 %s, %s, {x_hi}, %s bitop3:0x78" % (N[k], N[k], SC),
-              ["nn"], ["nn", "x"])
+            if not rng or cos:
+                a(k, "v_bitop3_b32 %s, %s, {x_hi}, %s bitop3:0x78" % (N[k], N[k], SC),
+                  ["nn"], ["nn", "x"])
             if self.salu:
                 a(k, "v_cmpx_gt_f64_e64 vcc, @C0126@, |{x}|\n"
                      "s_andn2_b64 %s, %s, exec\n"
@@ -1714,18 +1783,23 @@ class Gen(object):
             a(k, "v_fma_f64 {q}, {q}, {xx2}, {da}", ["q"], ["q", "xx2", "da"])
             a(k, "v_add_f64 {x}, |{x}|, {q}", [], ["x", "q"])
             a(k, lab + ":")
-        a(1, "s_mov_b64 exec, %s\ns_waitcnt lgkmcnt(0)" % SV)
+        cs = small and cos               # (EXEC never left the handler's)
+        a(1, "s_waitcnt lgkmcnt(0)" if cs else
+          "s_mov_b64 exec, %s\ns_waitcnt lgkmcnt(0)" % SV)
         if self.prio and self.prio_late and TRIG_DROP == "wait":
             a(1, "s_setprio %d" % self.prio[1])
         both("v_fma_f64 {cor}, {s}, {TBb}, {TAa}", ["cor"], ["s", "EB", "EA"])
         both("v_fma_f64 {cor}, -{w}, {TA}, {cor}", ["cor"], ["w", "EA", "cor"])
         both("v_fma_f64 {cor}, {s}, {TB}, {cor}", ["cor"], ["s", "EB", "cor"])
         for k in range(2):
-            a(k, "s_mov_b64 exec, %s" % M[k])
+            if not cs:
+                a(k, "s_mov_b64 exec, %s" % M[k])
             a(k, "v_add_f64 {x}, {TA}, {cor}", [], ["EA", "cor", "x"])
-        a(1, "s_mov_b64 exec, %s" % SV)
-        # the sign: n's bit 31 (negation xor a's sign for do_sin)
-        for k in range(2):
+        if not cs:
+            a(1, "s_mov_b64 exec, %s" % SV)
+        # the sign: n's bit 31 (negation xor a's sign for do_sin; cos small:
+        # n = 0, do_cos's result as it is)
+        for k in range(0 if cs else 2):
             a(k, "v_bitop3_b32 {x_hi}, {x_hi}, %s, %s bitop3:0x78" % (N[k], SC),
               [], ["x", "nn"])
         if os.environ.get("GEN_ASM_EXPERIMENT") == "ulp1":
@@ -2017,7 +2091,7 @@ class Gen(object):
         seq.append((ks[0], label + ":", (), ()))
         return seq
 
-    def sincos(self, want, mixed=False):
+    def sincos(self, want, mixed=False, rng=None):
         """The K chains of gp_trig, registers linear-scan allocated from the
         temporary pool: interleaved instruction by instruction in the fast
         body; one after the other in the (rare) mixed body, which keeps its
@@ -2025,8 +2099,9 @@ class Gen(object):
         two table reads are the youngest LDS operations at its waits."""
         K = self.K
         if self.exact and GLIBC4 and not mixed:
-            self._alloc_emit(self.glibc_seq4(want))
+            self._alloc_emit(self.glibc_seq4(want, rng))
             return
+        assert rng is None
         if self.exact and GLIBC3 and not mixed:
             self._alloc_emit(self.glibc_seq3(want))
             return
@@ -2396,6 +2471,38 @@ class Gen(object):
         self.e("s_branch .Lnext_%=")
 
     # ----------------------------------------------------------- build --
+    # the range-specialised sin/cos handler ids, after COS in every core with
+    # sin/cos (one translator layout): the host's range pass (trig_ranges.h)
+    # picks them per node
+    RANGE_HANDLERS = [("sin", "mid"), ("cos", "mid"), ("sin", "small"),
+                      ("cos", "small")]
+
+    def range_handlers(self):
+        """SIN_MID, COS_MID, SIN_SMALL, COS_SMALL.  The exact cores with
+        glibc_seq4's default scheme carry the specialised bodies
+        (glibc_seq4(rng=...)); in every other core the ids alias the general
+        handler: an entry of their own (every table offset is distinct and
+        starts a handler's dispatch) that joins it after its first
+        instruction.  GEN_ASM_TRIG_RANGES=0 (a variant build): aliases in the
+        exact cores too."""
+        real = getattr(self, "exact", False) and GLIBC4 and self.salu and \
+            os.environ.get("GEN_ASM_EXACT_SEQ") != "1" and \
+            os.environ.get("GEN_ASM_TRIG_RANGES", "1") == "1"
+        for want, rng in self.RANGE_HANDLERS:
+            name = "%s_%s" % (want.upper(), rng.upper())
+            self.handler(name)
+            if not real:
+                self.e("s_movrels_b32 s%d, s%d" % (self.TGT, self.WIN))
+                self.e("s_branch .Lalias_%s_%%=" % want.upper())
+                continue
+            self.dispatch_head()
+            self.e("s_waitcnt lgkmcnt(0)")
+            self.sincos(want, rng=rng)
+            if self.prio:                # (the body drops it after its gathers)
+                self.e("s_setprio %d" % self.prio[0])
+            self.dispatch_tail()
+            self.flush_ool()
+
     def build(self):
         K, D, NV = self.K, self.D, self.NV
         P = self.p
@@ -2581,7 +2688,7 @@ class Gen(object):
                 self.dispatch_tail()
         for want in (() if self.typed else ("sin", "cos")):
             self.handler(want.upper())
-            self.dispatch_head()
+            self.dispatch_head(alias_entry=".Lalias_%s_" % want.upper())
             self.e("s_waitcnt lgkmcnt(0)")
             if self.exact:                 # glibc's sin/cos, chains interleaved
                 if not GLIBC2:             # (glibc_ops2 keeps VRED itself)
@@ -2616,6 +2723,8 @@ class Gen(object):
             if self.prio:
                 self.e("s_setprio %d" % self.prio[0])
             self.dispatch_tail()
+        if not self.typed:
+            self.range_handlers()
         # ---- probe: write the handler offset table
         self.label(".Lprobe_")
         self.probe_stores(self.POOL0, self.POOL0 + 1)
@@ -2660,6 +2769,10 @@ class Gen(object):
                "H_PUSHV0": base_pushv, "H_BIN0": base_bin,
                "H_FAM_STRIDE": stride, "H_NEG": ids["NEG"],
                "H_SIN": ids.get("SIN", -1), "H_COS": ids.get("COS", -1),
+               "H_SIN_MID": ids.get("SIN_MID", -1),
+               "H_COS_MID": ids.get("COS_MID", -1),
+               "H_SIN_SMALL": ids.get("SIN_SMALL", -1),
+               "H_COS_SMALL": ids.get("COS_SMALL", -1),
                "H_COUNT": len(names), "WINDOW": WINDOW,
                "SGPR_BASE": self.BASE,
                "LIM_HI": LIM_HI, "FAST_HI": FAST_HI}

@@ -390,13 +390,14 @@ class Gen32(gen_asm.Gen):
         self.dispatch_tail()
         for want in ("sin", "cos"):
             self.handler(want.upper())
-            self.dispatch_head()
+            self.dispatch_head(alias_entry=".Lalias_%s_" % want.upper())
             if self.prio:
                 self.e("s_setprio %d" % self.prio[1])
             self.sincos(want)
             if self.prio:
                 self.e("s_setprio %d" % self.prio[0])
             self.dispatch_tail()
+        self.range_handlers()          # (aliases of SIN / COS: one layout)
         self.label(".Lprobe_")
         self.probe_stores(self.POOL0, self.POOL0 + 1)
         self.label(".Lend_")

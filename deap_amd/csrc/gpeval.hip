@@ -58,6 +58,7 @@
 
 #include "../../include/gpeval.h"
 #include "lower_core.h"
+#include "trig_ranges.h"
 #include "gp_asm_core.inc"
 #include "gp_asm_core32.inc"
 #include "gp_asm_core_deep.inc"
@@ -524,13 +525,29 @@ struct CoreIds {
   int D, NV, H_END, H_RELOAD, H_LDC, H_LDV0, H_PUSH0, H_PUSHC0, H_PUSHV0, H_BIN0,
       H_FAM_STRIDE, H_NEG, H_SIN, H_COS, H_COUNT;
   int H_NOT = -1, H_ITE0 = -1;      // the typed core only
+  // [class][cos]: the sin/cos handler of a trig_ranges class (general, mid,
+  // small); the cores without specialised bodies alias SIN / COS there
+  int H_TRIG[3][2] = {{-1, -1}, {-1, -1}, {-1, -1}};
 };
 #define CORE_IDS(NS)                                                          \
   CoreIds {                                                                   \
     NS::D, NS::NV, NS::H_END, NS::H_RELOAD, NS::H_LDC, NS::H_LDV0, NS::H_PUSH0, \
         NS::H_PUSHC0, NS::H_PUSHV0, NS::H_BIN0, NS::H_FAM_STRIDE, NS::H_NEG,    \
-        NS::H_SIN, NS::H_COS, NS::H_COUNT                                      \
+        NS::H_SIN, NS::H_COS, NS::H_COUNT, -1, -1,                             \
+    {                                                                         \
+      {NS::H_SIN, NS::H_COS}, {NS::H_SIN_MID, NS::H_COS_MID},                 \
+          {NS::H_SIN_SMALL, NS::H_COS_SMALL}                                  \
+    }                                                                         \
   }
+static_assert(asmcore::H_SIN_MID == asmcore::H_COS + 1 &&
+                  asmcore::H_COS_SMALL == asmcore::H_COUNT - 1 &&
+                  asmcore_exact::H_SIN_MID == asmcore::H_SIN_MID &&
+                  asmcore_exact::H_COS_SMALL == asmcore::H_COS_SMALL &&
+                  asmcore_exact_deep::H_SIN_MID == asmcore_deep::H_SIN_MID &&
+                  asmcore_exact_deep::H_COS_SMALL == asmcore_deep::H_COS_SMALL &&
+                  asmcore32::H_COS_SMALL == asmcore::H_COS_SMALL &&
+                  asmcore32_deep::H_COS_SMALL == asmcore_deep::H_COS_SMALL,
+              "the range-specialised sin/cos ids follow COS in every core's layout");
 constexpr CoreIds kIds = CORE_IDS(asmcore);
 constexpr CoreIds kIdsDeep = CORE_IDS(asmcore_deep);
 constexpr CoreIds kIdsExactDeep = CORE_IDS(asmcore_exact_deep);
@@ -538,7 +555,7 @@ constexpr CoreIds kIdsTyped = [] {
   CoreIds c = CORE_IDS(asmcore_typed);
   c.H_NOT = asmcore_typed::H_NOT;
   c.H_ITE0 = asmcore_typed::H_ITE0;
-  return c;
+  return c;                              // (no sin/cos: H_TRIG stays -1)
 }();
 static_assert(asmcore_typed::WINDOW == asmcore::WINDOW, "one window size");
 static_assert(asmcore32::H_COUNT == asmcore::H_COUNT &&
@@ -610,18 +627,27 @@ __global__ __launch_bounds__(256) void const_hits(const uint32_t* kc, int64_t n,
 // (END pads the rest); the program starts on a window boundary.  Returns the
 // length; writes the words when `out` is not null.  The same code runs on
 // the host (gpe_debug_translate, tests) and in translate_kernel.
+// `bnd` (the exact cores, while writing): the case columns' (lo, hi), nb of
+// them — every sin/cos word is then the handler of its argument's proven
+// range (trig_ranges.h), counted per class into `cls3` when given; null:
+// every sin/cos is the general handler.  The word count is the same.
 HD int64_t translate_words(const uint32_t* w, const uint32_t* tab, const CoreIds& I,
-                           bool f32, int window_use, uint32_t* out) {
+                           bool f32, int window_use, uint32_t* out,
+                           const double* bnd = nullptr, int nb = 0,
+                           uint32_t* cls3 = nullptr) {
   constexpr int WINDOW = asmcore::WINDOW;
   const int D = I.D, NV = I.NV;
   int64_t n = 0;
   int pos = 0;
+  const bool ranges = bnd != nullptr && out != nullptr;
+  trig_ranges::Walk R(bnd, ranges ? nb : 0);
   auto emit = [&](uint32_t v) {
     if (out) out[n] = v;
     ++n;
   };
   for (;;) {
     const uint32_t op = w[0] & 0xffu, d = (w[0] >> 8) & 0xffu, x = w[0] >> 16;
+    const uint32_t word = w[0];
     ++w;
     int h;
     bool konst = false;
@@ -661,6 +687,15 @@ HD int64_t translate_words(const uint32_t* w, const uint32_t* tab, const CoreIds
       h = form == 0 ? base + (int)d : form == 1 ? base + D + (int)x : base + D + NV;
       konst = form == 2;
     }
+    if (ranges) {
+      const int c = R.step(word, konst ? w[0] : 0u, konst ? w[1] : 0u);
+      if (c >= 0) {
+        h = I.H_TRIG[c][op == OP_COS ? 1 : 0];
+        if (cls3) ++cls3[c];
+      }
+    } else if (cls3 && out && (op == OP_SIN || op == OP_COS)) {
+      ++cls3[0];                              // (no bounds: all general)
+    }
     const int need = konst ? 3 : 1;
     if (pos + need > window_use) {            // next word would leave it
       emit(tab[I.H_RELOAD]);
@@ -694,11 +729,11 @@ int window_use() {
 
 void translate_program(const uint32_t* w, const std::vector<uint32_t>& tab,
                        std::vector<uint32_t>& out, bool f32 = false,
-                       const CoreIds& I = kIds) {
+                       const CoreIds& I = kIds, const double* bnd = nullptr, int nb = 0) {
   const int64_t n = translate_words(w, tab.data(), I, f32, window_use(), nullptr);
   const size_t base = out.size();
   out.resize(base + (size_t)n);
-  translate_words(w, tab.data(), I, f32, window_use(), out.data() + base);
+  translate_words(w, tab.data(), I, f32, window_use(), out.data() + base, bnd, nb);
 }
 
 // Device translation (translate_device): per program, its core class
@@ -711,7 +746,8 @@ struct XlateTabs {
 __global__ __launch_bounds__(256) void translate_kernel(
     const uint32_t* code, const int64_t* off, const uint8_t* cls, int64_t n,
     XlateTabs T, int f32, int wuse, int pass, uint32_t* len, const uint32_t* start,
-    uint32_t* out, uint8_t* typed_ok) {
+    uint32_t* out, uint8_t* typed_ok, const double* bnd, int nb,
+    unsigned long long* trig_cls) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t* w = code + off[i];
@@ -737,16 +773,25 @@ __global__ __launch_bounds__(256) void translate_kernel(
   const int t = c == 3 ? 2 : c - 1;
   if (pass == 0)
     len[i] = (uint32_t)translate_words(w, T.tab[t], T.ids[t], f32 != 0, wuse, nullptr);
-  else
+  else if (!trig_cls)
     translate_words(w, T.tab[t], T.ids[t], f32 != 0, wuse, out + start[i]);
+  else {
+    uint32_t c3[3] = {0, 0, 0};
+    translate_words(w, T.tab[t], T.ids[t], f32 != 0, wuse, out + start[i], bnd, nb, c3);
+    for (int k = 0; k < 3; ++k)
+      if (c3[k]) atomicAdd(trig_cls + k, (unsigned long long)c3[k]);
+  }
 }
 
 // Threaded code of programs (classes `cls` on the host: 1/2 for the two
 // tables given; typed: the typed core decides) into (d_out, d_start), from
 // the words already on the device: no host copy of the programs.
+// `ranges`: the exact cores' translation — sin/cos words by proven range
+// (ctx->d_col_bnd, GPE_TRIG_RANGES), the classes counted into
+// ctx->trig_classes (gpe_last_trig_classes).
 int translate_device(gpe_ctx* ctx, const std::vector<uint8_t>* cls, const XlateTabs& T,
                      bool f32, bool typed, uint32_t** d_out, size_t* out_cap,
-                     uint32_t** d_start, size_t* start_cap) {
+                     uint32_t** d_start, size_t* start_cap, bool ranges = false) {
   const int64_t n = ctx->n_prog;
   const auto t_x0 = std::chrono::steady_clock::now();
   const unsigned blocks = (unsigned)((std::max<int64_t>(n, 1) + 255) / 256);
@@ -774,7 +819,7 @@ int translate_device(gpe_ctx* ctx, const std::vector<uint8_t>* cls, const XlateT
   HIPCHK(hipMemsetAsync(ctx->d_xl_len + n, 0, sizeof(uint32_t), ctx->stream));
   hipLaunchKernelGGL(translate_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->d_code,
                      ctx->d_off, d_cls, n, T, f32 ? 1 : 0, window_use(), 0, ctx->d_xl_len,
-                     nullptr, nullptr, d_typed);
+                     nullptr, nullptr, d_typed, nullptr, 0, nullptr);
   HIPCHK(hipGetLastError());
   if (ctx->diag) {
     HIPCHK(hipEventRecord(ctx->ev_redo[1], ctx->stream));
@@ -815,15 +860,32 @@ int translate_device(gpe_ctx* ctx, const std::vector<uint8_t>* cls, const XlateT
                 .count());
   const size_t words = (size_t)total + 2 * asmcore::WINDOW;   // s_load_dwordx16 slack
   if (ensure(ctx, d_out, out_cap, words)) return GPE_E_HIP;
+  const bool use_bnd = ranges && ctx->trig_ranges && ctx->d_col_bnd && ctx->d_trig_cls;
+  if (ranges) ctx->trig_classes[0] = ctx->trig_classes[1] = ctx->trig_classes[2] = 0;
+  if (ranges && ctx->d_trig_cls)
+    HIPCHK(hipMemsetAsync(ctx->d_trig_cls, 0, 3 * sizeof(unsigned long long), ctx->stream));
+  // (with the switch off the classes are still counted: all general)
   hipLaunchKernelGGL(translate_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->d_code,
                      ctx->d_off, d_cls, n, T, f32 ? 1 : 0, window_use(), 1, ctx->d_xl_len,
-                     *d_start, *d_out, d_typed);
+                     *d_start, *d_out, d_typed,
+                     use_bnd ? (const double*)ctx->d_col_bnd : nullptr, ctx->nv,
+                     ranges ? ctx->d_trig_cls : nullptr);
   HIPCHK(hipGetLastError());
+  // the class counts ride in the pinned header (bytes 32..55; the total was
+  // read above) and are read after this function's last synchronisation
+  if (ranges && ctx->d_trig_cls)
+    HIPCHK(hipMemcpyAsync(pin + 32, ctx->d_trig_cls, 3 * sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, ctx->stream));
   const uint32_t end_word = T.tab[typed ? 2 : 0][T.ids[typed ? 2 : 0].H_END];
   std::vector<uint32_t> slack(2 * asmcore::WINDOW, end_word);
   HIPCHK(hipMemcpyAsync(*d_out + total, slack.data(), slack.size() * sizeof(uint32_t),
                         hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (ranges && ctx->d_trig_cls) {
+    unsigned long long c3[3];
+    std::memcpy(c3, pin + 32, sizeof(c3));
+    for (int k = 0; k < 3; ++k) ctx->trig_classes[k] = (int64_t)c3[k];
+  }
   return 0;
 }
 
@@ -1565,6 +1627,7 @@ int gpe_create(int device, gpe_ctx** out) {
     ctx->div_w = atoi(env);
   if ((env = getenv("GPE_DIAG"))) ctx->diag = atoi(env);
   if ((env = getenv("GPE_EXACT_ALL"))) ctx->exact_all = atoi(env) != 0;
+  if ((env = getenv("GPE_TRIG_RANGES"))) ctx->trig_ranges = atoi(env) != 0;
   if ((env = getenv("GPE_REDO_EXP")) && atoi(env) >= 14 && atoi(env) <= 40)
     ctx->redo_hi = (uint32_t)(0x3ff + atoi(env)) << 20;
   if ((env = getenv("GPE_REDO_EXP_DEEP")) && atoi(env) >= 14 && atoi(env) <= 40)
@@ -1642,7 +1705,8 @@ void gpe_destroy(gpe_ctx* ctx) {
                   ctx->d_acode_t, ctx->d_astart_t, ctx->d_xl_len, ctx->d_xl_cls,
                   ctx->d_jump_asm, ctx->d_jump_asm_deep, ctx->d_jump_asm_exact,
                   ctx->d_jump_asm32, ctx->d_jump_asm32_deep, ctx->d_jump_asm_typed,
-                  ctx->d_jump_asm_exact_deep, ctx->d_redo_nsel, ctx->d_kc, ctx->d_exh_rec};
+                  ctx->d_jump_asm_exact_deep, ctx->d_redo_nsel, ctx->d_kc, ctx->d_exh_rec,
+                  ctx->d_col_bnd, ctx->d_trig_cls};
   if (ctx->comm && rccl().ok) (void)rccl().comm_destroy(ctx->comm);
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -1711,6 +1775,12 @@ int gpe_set_cases(gpe_ctx* ctx, int machine, const void* X, int n_vars,
   ctx->ex_hcases = false;      // (the host exact pass copies them on need)
   ctx->n_prog = 0;
   ctx->planned_mode = -1;
+  // the columns' bounds belong to the cases (trig_ranges.h): none until the
+  // new ones are in place
+  if (ctx->d_col_bnd) HIPCHK(hipFree(ctx->d_col_bnd));
+  ctx->d_col_bnd = nullptr;
+  ctx->col_bnd.clear();
+  ctx->trig_classes[0] = ctx->trig_classes[1] = ctx->trig_classes[2] = 0;
   size_t xb, tb;
   if (machine == GPE_MACHINE_F) {
     ctx->nt = n_terms;
@@ -1738,6 +1808,38 @@ int gpe_set_cases(gpe_ctx* ctx, int machine, const void* X, int n_vars,
                        dim3(256), 0, ctx->stream, (double*)ctx->d_X, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  if (machine == GPE_MACHINE_F && n_vars > 0) {
+    // [min, max] of every variable column, hulled with 0.0 (f_stage pads a
+    // partial last tile with 0.0 and the pad lanes run the handlers too); a
+    // column holding a nan or an inf is unbounded.  Columns [nv, 3 nv): the
+    // trig leaves sin(x_v), cos(x_v) — within [-1, 1] when x_v is bounded.
+    const double* Xh = (const double*)X;
+    const double inf = __builtin_inf();
+    ctx->col_bnd.assign((size_t)6 * n_vars, 0.0);
+    std::vector<double>& B = ctx->col_bnd;
+    hostpool::par_run(n_vars, [&](int v) {
+      double lo = 0.0, hi = 0.0;
+      bool bad = false;
+      const double* col = Xh + (int64_t)v * n_cases;
+      for (int64_t c = 0; c < n_cases; ++c) {
+        const double t = col[c];
+        bad |= !(t - t == 0.0);              // nan, +-inf
+        lo = t < lo ? t : lo;
+        hi = t > hi ? t : hi;
+      }
+      B[2 * (size_t)v] = bad ? -inf : lo;
+      B[2 * (size_t)v + 1] = bad ? inf : hi;
+      for (int k = 1; k <= 2; ++k) {
+        B[2 * ((size_t)k * n_vars + v)] = bad ? -inf : -1.0;
+        B[2 * ((size_t)k * n_vars + v) + 1] = bad ? inf : 1.0;
+      }
+    });
+    HIPCHK(hipMalloc((void**)&ctx->d_col_bnd, B.size() * sizeof(double)));
+    HIPCHK(hipMemcpy(ctx->d_col_bnd, B.data(), B.size() * sizeof(double),
+                     hipMemcpyHostToDevice));
+    if (!ctx->d_trig_cls)
+      HIPCHK(hipMalloc((void**)&ctx->d_trig_cls, 3 * sizeof(unsigned long long)));
   }
   // the first target column's truths (HITS_BOOL: a constant program's hits)
   ctx->label_true = 0;
@@ -3253,6 +3355,23 @@ int gpe_debug_translate(const uint32_t* code, int64_t n_words,
                         const int32_t* depth, int nv, const uint32_t* table,
                         int n_table, uint32_t* out, int64_t out_cap,
                         int64_t* starts, int64_t* n_out) {
+  return gpe_debug_translate_ranges(code, n_words, off, n_prog, depth, nv, table, n_table,
+                                    out, out_cap, starts, n_out, nullptr, nullptr);
+}
+
+int gpe_debug_translate_ranges(const uint32_t* code, int64_t n_words,
+                               const int64_t* off, int64_t n_prog,
+                               const int32_t* depth, int nv, const uint32_t* table,
+                               int n_table, uint32_t* out, int64_t out_cap,
+                               int64_t* starts, int64_t* n_out, const double* lo,
+                               const double* hi) {
+  if ((lo == nullptr) != (hi == nullptr)) return GPE_E_INVALID;
+  std::vector<double> bnd;
+  if (lo)
+    for (int v = 0; v < nv; ++v) {
+      bnd.push_back(lo[v]);
+      bnd.push_back(hi[v]);
+    }
   if (!code || !off || !depth || !table || !out || !starts || !n_out ||
       (n_table != asmcore::H_COUNT && n_table != asmcore_deep::H_COUNT))
     return GPE_E_INVALID;
@@ -3269,11 +3388,46 @@ int gpe_debug_translate(const uint32_t* code, int64_t n_words,
     starts[i] = -1;
     if (!ok || (!deep_core && depth[i] > asmcore::D)) continue;
     starts[i] = (int64_t)acode.size();
-    translate_program(code + off[i], tab, acode, false, deep_core ? kIdsDeep : kIds);
+    translate_program(code + off[i], tab, acode, false, deep_core ? kIdsDeep : kIds,
+                      lo ? bnd.data() : nullptr, nv);
   }
   if ((int64_t)acode.size() > out_cap) return GPE_E_INVALID;
   std::copy(acode.begin(), acode.end(), out);
   *n_out = (int64_t)acode.size();
+  return 0;
+}
+
+int gpe_debug_trig_classes(const uint32_t* code, int64_t n_words, const double* lo,
+                           const double* hi, int nv, int32_t* out, int64_t cap) {
+  if (!code || n_words <= 0 || nv < 0 || (nv && (!lo || !hi)) || (cap && !out) || cap < 0)
+    return -1;
+  std::vector<double> bnd;
+  for (int v = 0; v < nv; ++v) {
+    bnd.push_back(lo[v]);
+    bnd.push_back(hi[v]);
+  }
+  trig_ranges::Walk R(bnd.data(), nv);
+  int64_t n = 0;
+  for (int64_t i = 0; i < n_words;) {
+    const uint32_t w = code[i], op = w & 0xffu;
+    if (op == OP_END) return (int)n;
+    const bool bin = (op >= OP_ADD && op < OP_XOR) || op >= OP_NPDIV;
+    const bool konst = op == OP_LDC || op == OP_PUSHC ||
+                       (bin && (op - (op >= OP_NPDIV ? OP_NPDIV : OP_ADD)) % 3 == 2);
+    if (konst && i + 2 >= n_words) return -1;
+    const int c = R.step(w, konst ? code[i + 1] : 0u, konst ? code[i + 2] : 0u);
+    if (c >= 0) {
+      if (n < cap) out[n] = c;
+      ++n;
+    }
+    i += konst ? 3 : 1;
+  }
+  return -1;                                  // no END
+}
+
+int gpe_last_trig_classes(const gpe_ctx* ctx, int64_t* out) {
+  if (!ctx || !out) return GPE_E_INVALID;
+  for (int k = 0; k < 3; ++k) out[k] = ctx->trig_classes[k];
   return 0;
 }
 

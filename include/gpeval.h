@@ -404,6 +404,33 @@ int gpe_debug_translate(const uint32_t* code, int64_t n_words,
                         int n_table, uint32_t* out, int64_t out_cap,
                         int64_t* starts, int64_t* n_out);
 
+/* gpe_debug_translate as the exact cores' translation runs it: with the case
+ * columns' bounds lo[v], hi[v] (v < nv), every sin/cos word is the handler
+ * of its argument's proven range (the table's SIN_MID, COS_MID, SIN_SMALL,
+ * COS_SMALL entries after COS); lo == hi == NULL: gpe_debug_translate.  The
+ * word count never depends on the bounds. */
+int gpe_debug_translate_ranges(const uint32_t* code, int64_t n_words,
+                               const int64_t* off, int64_t n_prog,
+                               const int32_t* depth, int nv, const uint32_t* table,
+                               int n_table, uint32_t* out, int64_t out_cap,
+                               int64_t* starts, int64_t* n_out, const double* lo,
+                               const double* hi);
+
+/* Diagnostic (host only, no context): the range pass over one F-machine
+ * program (n_words flattener words ending in END) with column bounds lo[v],
+ * hi[v] (v < nv; an infinite bound: unbounded).  Writes the class of each
+ * sin/cos node in word order — 0 general, 1 mid (|x| < 2.42 proven in every
+ * lane), 2 small (|x| < 0.855) — into out[0 .. cap) and returns their number,
+ * or -1 for a malformed program. */
+int gpe_debug_trig_classes(const uint32_t* code, int64_t n_words, const double* lo,
+                           const double* hi, int nv, int32_t* out, int64_t cap);
+
+/* The sin/cos words of the last exact-core translation per class: out[0]
+ * general, out[1] mid, out[2] small handlers (GPE_TRIG_RANGES=0, read once
+ * by gpe_create: all general).  The column bounds the classes are proven
+ * from are those of the last gpe_set_cases. */
+int gpe_last_trig_classes(const gpe_ctx* ctx, int64_t* out);
+
 /* Diagnostic: evaluate the device's sin (fn 0), cos (fn 1), square (fn 2),
  * the platform libm's sin (3) / cos (4), or sin (5) / cos (6) through the
  * hand-scheduled asm interpreter core; fp32 mode: sin (7) / cos (8) through

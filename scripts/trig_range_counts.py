@@ -1,0 +1,160 @@
+#!/usr/bin/env python3
+"""Executed instructions per sin/cos call of the exact cores' handlers, with
+and without the range-specialised ones, on headline trees and their own
+arguments (tests/asm_emu.py on the CPU; no GPU).
+
+The first ``trees`` trees of the headline population (bench.py's seed and
+depths) are flattened; the range pass (csrc/trig_ranges.h, through
+gpe_debug_trig_classes) classifies every sin/cos node from the columns'
+bounds [-1, 1]; the words are evaluated on the first ``tiles`` 128-case tiles
+of the headline cases, and every sin/cos call's 128 arguments (chain k =
+cases 64k .. 64k + 63) run through the general handler and through the
+handler of the node's class.  Prints, per handler, the executed VALU (of
+them fp64), SALU and LDS instructions per wave-call, the class shares, and
+the weighted per-call totals of the specialised mix against the general
+handler alone.  Every result is checked bit for bit against the host libm,
+and every argument against its class's range.
+
+Usage: python scripts/trig_range_counts.py [trees=192] [tiles=2]
+"""
+import math
+import os
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "tests"))
+sys.path.insert(1, REPO)
+
+import asm_emu                                   # noqa: E402
+from deap_amd import _lib, configs              # noqa: E402
+from deap_amd.flatten import Flattener, Op       # noqa: E402
+
+CLASS = ("general", "mid", "small")
+LIMIT = (math.inf, 2.42, 0.855)
+
+
+def f64(lo, hi):
+    return np.array([int(lo) | (int(hi) << 32)], dtype=np.uint64).view(np.float64)[0]
+
+
+def pdiv(num, den):
+    z = den == 0.0
+    return np.where(z, 1.0, num / np.where(z, 1.0, den))
+
+
+def trig_calls(words, X):
+    """(kind, arguments per case) of every sin/cos word, in word order."""
+    n = X.shape[1]
+    T, R, out, pc = np.zeros(n), {}, [], 0
+    with np.errstate(all="ignore"):
+        while True:
+            w = int(words[pc])
+            pc += 1
+            op, d, x = w & 0xff, (w >> 8) & 0xff, w >> 16
+            if op == Op.END:
+                return out
+            form = (op - Op.ADD) % 3 if Op.ADD <= op < Op.NEG else -1
+            c = None
+            if op in (Op.LDC, Op.PUSHC) or form == 2:
+                c = f64(words[pc], words[pc + 1])
+                pc += 2
+            if op in (Op.PUSH, Op.PUSHV, Op.PUSHC):
+                R[d] = T
+            if op in (Op.LDV, Op.PUSHV):
+                T = X[x].copy()
+            elif op in (Op.LDC, Op.PUSHC):
+                T = np.full(n, c)
+            elif op == Op.NEG:
+                T = -T
+            elif op in (Op.SIN, Op.COS):
+                out.append(("sin" if op == Op.SIN else "cos", T.copy()))
+                fn = math.sin if op == Op.SIN else math.cos
+                T = np.array([fn(v) if math.isfinite(v) else math.nan for v in T.tolist()])
+            elif form >= 0:
+                a = R[d] if form == 0 else X[x] if form == 1 else np.full(n, c)
+                fam = (op - Op.ADD) // 3        # add sub rsub mul div rdiv
+                T = [a + T, a - T, T - a, a * T, pdiv(a, T), pdiv(T, a)][fam] \
+                    if fam < 6 else None
+                assert T is not None, "an op outside the symreg10 set"
+            elif op != Op.PUSH:
+                raise ValueError(op)
+
+
+def main():
+    n_trees = int(sys.argv[1]) if len(sys.argv) > 1 else 192
+    tiles = int(sys.argv[2]) if len(sys.argv) > 2 else 2
+    pset = configs.pset_for("symreg10")
+    pop = configs.population(pset, "half", n_trees, 2024, 4, 8)
+    batch = Flattener(pset).flatten(pop)
+    code = np.asarray(batch.code, dtype=np.uint32)
+    off = np.asarray(batch.offsets, dtype=np.int64)
+    X = np.ascontiguousarray(np.random.default_rng(2024).uniform(
+        -1.0, 1.0, size=(tiles * 128, 10)).T)
+    lo, hi = -np.ones(10), np.ones(10)
+    names = {(k, c): (k.upper() if c == 0 else "%s_%s" % (k.upper(), CLASS[c].upper()))
+             for k in ("sin", "cos") for c in range(3)}
+    lines = {h: asm_emu.handler_lines(h) for h in names.values()}
+    spec = {h: {} for h in names.values()}       # the node's class handler
+    gen = {h: {} for h in names.values()}        # the general one, same calls
+    calls = {h: 0 for h in names.values()}
+    bad = 0
+    for i in range(n_trees):
+        w = code[off[i]:off[i + 1]]
+        cls = _lib.debug_trig_classes(w, lo, hi)
+        got = trig_calls(w, X)
+        assert len(cls) == len(got)
+        for c, (kind, arg) in zip(cls.tolist(), got):
+            h = names[(kind, c)]
+            f = math.sin if kind == "sin" else math.cos
+            for t in range(tiles):
+                x = np.ascontiguousarray(arg[t * 128:(t + 1) * 128])
+                if not np.isfinite(x).all():
+                    assert c == 0
+                    continue
+                assert np.abs(x).max() < LIMIT[c], (str(pop[i]), CLASS[c])
+                ref = np.array([f(v) for v in x.tolist()]).view(np.uint64)
+                y, _ = asm_emu.run_handler(h, x, lines=lines[h], counts=spec[h])
+                bad += int((y.view(np.uint64) != ref).sum())
+                g = names[(kind, 0)]
+                if c:
+                    y, _ = asm_emu.run_handler(g, x, lines=lines[g], counts=gen[h])
+                    bad += int((y.view(np.uint64) != ref).sum())
+                calls[h] += 1
+    total = sum(calls.values())
+    print("%d trees, %d tiles: %d sin/cos wave-calls; results not the host "
+          "libm's: %d" % (n_trees, tiles, total, bad))
+    print("| handler | share of calls | VALU | of them fp64 | SALU | LDS | "
+          "general handler on the same calls: VALU / fp64 / SALU |")
+    print("|---|---|---|---|---|---|---|")
+    tot_s = {"valu": 0, "valu_f64": 0, "salu": 0, "lds": 0}
+    tot_g = dict(tot_s)
+    for h in sorted(calls, key=lambda s: (s[4:] or "0", s)):
+        n = calls[h]
+        if not n:
+            continue
+        s = spec[h]
+        g = gen[h] if "_" in h else s
+        for k in tot_s:
+            tot_s[k] += s.get(k, 0)
+            tot_g[k] += g.get(k, 0)
+        print("| %s | %.1f %% | %.1f | %.1f | %.1f | %.1f | %s |"
+              % (h, 100.0 * n / total, s.get("valu", 0) / n, s.get("valu_f64", 0) / n,
+                 s.get("salu", 0) / n, s.get("lds", 0) / n,
+                 "—" if "_" not in h else "%.1f / %.1f / %.1f"
+                 % (g.get("valu", 0) / n, g.get("valu_f64", 0) / n, g.get("salu", 0) / n)))
+    print("| weighted, specialised mix | 100 %% | %.1f | %.1f | %.1f | %.1f | "
+          "%.1f / %.1f / %.1f |"
+          % (tot_s["valu"] / total, tot_s["valu_f64"] / total, tot_s["salu"] / total,
+             tot_s["lds"] / total, tot_g["valu"] / total, tot_g["valu_f64"] / total,
+             tot_g["salu"] / total))
+    print("VALU per average call: %.1f -> %.1f (%.1f %% fewer); SALU %.1f -> %.1f"
+          % (tot_g["valu"] / total, tot_s["valu"] / total,
+             100.0 * (1 - tot_s["valu"] / tot_g["valu"]),
+             tot_g["salu"] / total, tot_s["salu"] / total))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
