@@ -72,6 +72,10 @@ SIGNATURES = {
                                         _I64, _P, _P, _P, _P]),
     "gpe_debug_trig_classes": (_I, [_P, _I64, _P, _P, _I, _P, _I64]),
     "gpe_last_trig_classes": (_I, [_P, ctypes.POINTER(ctypes.c_int64)]),
+    "gpe_debug_translate_mode": (_I, [_P, _I64, _P, _I64, _P, _I, _P, _I, _P,
+                                         _I64, _P, _P, _P, _P, _I]),
+    "gpe_debug_trig_classes_mode": (_I, [_P, _I64, _P, _P, _I, _I, _P, _I64]),
+    "gpe_last_trig_picked": (_I, [_P, ctypes.POINTER(ctypes.c_int64)]),
     "gpe_comm_unique_id": (_I, [_P]),
     "gpe_comm_init": (_I, [_P, _I, _I, _P]),
     "gpe_comm_info": (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
@@ -164,28 +168,32 @@ def host_np_sum(rows):
 
 
 TRIG_CLASSES = ("general", "mid", "small")
+# the classes GPE_TRIG_RANGES=2 (the default) picks handlers by
+TRIG_PICKED = TRIG_CLASSES + ("midlo", "wide")
 
 
-def debug_trig_classes(words, lo, hi):
+def debug_trig_classes(words, lo, hi, mode=1):
     """Host-only: the range pass (csrc/trig_ranges.h) over one program's
-    flattener words with column bounds lo[v], hi[v]: the class index
-    (``TRIG_CLASSES``) of each sin/cos node, in word order."""
+    flattener words with column bounds lo[v], hi[v]: the class index of each
+    sin/cos node, in word order.  ``mode`` 1: the base classes
+    (``TRIG_CLASSES``); 2, the library's default: ``TRIG_PICKED``."""
     words = np.ascontiguousarray(words, dtype=np.uint32)
     lo = np.ascontiguousarray(lo, dtype=np.float64)
     hi = np.ascontiguousarray(hi, dtype=np.float64)
     assert lo.shape == hi.shape and lo.ndim == 1
     out = np.zeros(max(len(words), 1), dtype=np.int32)
-    n = load().gpe_debug_trig_classes(_ptr(words), len(words), _ptr(lo), _ptr(hi),
-                                      len(lo), _ptr(out), len(out))
+    n = load().gpe_debug_trig_classes_mode(_ptr(words), len(words), _ptr(lo), _ptr(hi),
+                                       len(lo), int(mode), _ptr(out), len(out))
     if n < 0:
         raise GpeError("gpe_debug_trig_classes: malformed program")
     return out[:n]
 
 
-def debug_translate(batch, nv, table, bounds=None):
+def debug_translate(batch, nv, table, bounds=None, mode=1):
     """Host-only: threaded code the asm core would run (see header).
     ``bounds`` = (lo, hi) per column: the exact cores' translation, sin/cos
-    words by proven range (gpe_debug_translate_ranges)."""
+    words by proven range (gpe_debug_translate_mode; ``mode`` as
+    ``debug_trig_classes``)."""
     lib = load()
     code = np.ascontiguousarray(batch.code, dtype=np.uint32)
     off = np.ascontiguousarray(batch.offsets, dtype=np.int64)
@@ -201,11 +209,11 @@ def debug_translate(batch, nv, table, bounds=None):
         lo = np.ascontiguousarray(bounds[0], dtype=np.float64)
         hi = np.ascontiguousarray(bounds[1], dtype=np.float64)
         assert len(lo) == len(hi) == int(nv)
-    rc = lib.gpe_debug_translate_ranges(
+    rc = lib.gpe_debug_translate_mode(
         _ptr(code), len(code), _ptr(off), len(depth), _ptr(depth), int(nv),
         _ptr(table), len(table), _ptr(out), cap, _ptr(starts),
         ctypes.byref(n_out), None if lo is None else _ptr(lo),
-        None if hi is None else _ptr(hi))
+        None if hi is None else _ptr(hi), int(mode))
     if rc != 0:
         raise GpeError("gpe_debug_translate failed (%d)" % rc)
     return out[:n_out.value], starts
@@ -762,9 +770,16 @@ class Context(object):
     LAUNCHES = ("asm_fast", "asm_deep", "typed", "cpp_fast", "cpp_deep",
                 "fasm", "dasm")
 
-    def trig_classes(self):
-        """sin/cos words of the last exact-core translation per class
-        (gpe_last_trig_classes): {"general", "mid", "small"}."""
+    def trig_classes(self, picked=False):
+        """sin/cos words of the last exact-core translation per base class
+        (gpe_last_trig_classes): {"general", "mid", "small"}; ``picked``: per
+        class whose handler was picked (gpe_last_trig_picked): those three
+        and {"midlo", "wide"}."""
+        if picked:
+            g = (ctypes.c_int64 * len(TRIG_PICKED))()
+            self._check(self.lib.gpe_last_trig_picked(self.h, g),
+                        "gpe_last_trig_picked")
+            return dict(zip(TRIG_PICKED, (int(v) for v in g)))
         g = (ctypes.c_int64 * 3)()
         self._check(self.lib.gpe_last_trig_classes(self.h, g),
                     "gpe_last_trig_classes")

@@ -328,15 +328,18 @@ struct gpe_ctx {
   int neg_fold = 1;            // lowering's NEG peephole (GPE_NEG_PEEPHOLE=0: off)
   int exact_all = 1;           // GPE_EXACT_ALL: the exact cores (0: table cores + redo)
   // range-specialised sin/cos handlers of the exact cores (trig_ranges.h;
-  // GPE_TRIG_RANGES=0: only the general handlers, the A/B control).  The F
-  // machine's column bounds, (lo, hi) per column of [0, 3 nv_user) (the trig
-  // leaves' columns included), set and reset by gpe_set_cases; the sin/cos
-  // words of the last exact-core translation per class (general, mid, small)
-  int trig_ranges = 1;
+  // GPE_TRIG_RANGES=0: only the general handlers; 1: SIN/COS_MID and _SMALL,
+  // the A/B control of the later ones; 2, the default: all — trig_ranges::
+  // Mode).  The F machine's column bounds, (lo, hi) per column of
+  // [0, 3 nv_user) (the trig leaves' columns included), set and reset by
+  // gpe_set_cases; the sin/cos words of the last exact-core translation: by
+  // base class (general, mid, small), then by the class picked (general, mid,
+  // small, midlo, wide)
+  int trig_ranges = 2;
   std::vector<double> col_bnd;
   double* d_col_bnd = nullptr;
   unsigned long long* d_trig_cls = nullptr;
-  int64_t trig_classes[3] = {0, 0, 0};
+  int64_t trig_classes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // gpe_debug_redo_union: redo flags "another rank" raised, ORed in where a
   // case-sharded run all-reduces them (test infrastructure)
   std::vector<uint32_t> debug_redo_or;

@@ -1446,13 +1446,29 @@ class Gen(object):
         ranges), so the do_sin lanes' sign fold goes.  "small"
         (|x| < 0.855): no compare, no d block; sin: do_sin(x, 0) for every
         lane (n = x.hi), cos: do_cos(x, 0) for every lane — no do_sin lanes,
-        no TAYLOR_SIN, no sign (n = 0).  da = 0 and its sign fold, and the
-        do_cos lanes' xr + da, stay: their removal is not an identity for
-        every signed zero by construction, and they are cheap."""
+        no TAYLOR_SIN, no sign (n = 0).  With da = +-0 every term da enters
+        is an identity on the bits (xr = |x| - q1 and w are never -0, so
+        xr + da = xr and w + da xr = w; m p + da and pt |x| - 0.5 da differ
+        from the bare products only in a zero's sign, which the following
+        + xr / |x| + q absorbs: both operands +0 or the other nonzero), so
+        "small" carries no da at all (tests/test_asm_emu_ranges_more.py: bit
+        equality on zeros, denormals, every binade and the 0.126 edge).
+        "midlo" (cos, |x| < 1.44): "mid" whose do_sin lanes (the d lanes,
+        0.85546875 <= |x|) have a = (hp0 - |x|) + hp1 >= pi/2 - 1.44 =
+        0.1308 > 0.126, so the 0.126 compare, its masks and TAYLOR_SIN go
+        and the table result is every lane's.
+        "wide" (every lane finite and |x| < 1e8 < 105414350): the general
+        body without the VRED update (VRED is read for the inf/nan exit and
+        the __branred test, neither of which such a lane can need), the
+        105414350 compare, its branch and the slow path."""
         assert self.K == 2 and GLIBC4
-        assert rng in (None, "mid", "small") and (rng is None or self.salu)
+        assert rng in (None, "mid", "small", "midlo", "wide") and \
+            (rng is None or self.salu)
         cos = want == "cos"
-        mid, small = rng == "mid", rng == "small"
+        midlo, wide = rng == "midlo", rng == "wide"
+        assert cos or not midlo
+        mid, small = rng in ("mid", "midlo"), rng == "small"
+        known = mid or small             # (wide: the general body's range tests)
         seq = []
         M = [self.sp(self.CA), self.sp(self.BASE)]
         SV = self.sp(self.SMASK)
@@ -1494,7 +1510,7 @@ class Gen(object):
                   [pfx + "y", "x", "da"])
                 a(k, "v_add_f64 {da}, {da}, @HP1@", ["da"], ["da"])
             else:
-                if not rng:              # (mid: set for all lanes before)
+                if not known:            # (mid: set for all lanes before)
                     a(k, "v_mov_b32_e32 %s, {x_hi}" % N[k], ["nn"], ["x", "nn"])
                 a(k, "v_add_f64 {x}, @HP0@, -|{x}|", [], ["x"])
                 a(k, "v_mov_b64_e32 {da}, @HP1@", ["da"], ["da"])
@@ -1539,8 +1555,9 @@ class Gen(object):
                 # (pricing: six more wave-uniform SALU per call, no dependences)
                 a(0, "\n".join(["s_mov_b64 %s, exec" % SV] * 6))
             both("v_and_b32_e32 {hx}, 0x7fffffff, {x_hi}", ["hx"], ["x"])
-            a(1, "v_max3_u32 v%d, v%d, {hx@0}, {hx}" % (self.VRED, self.VRED),
-              [], ["hx@0", "hx"])
+            if not wide:
+                a(1, "v_max3_u32 v%d, v%d, {hx@0}, {hx}" % (self.VRED, self.VRED),
+                  [], ["hx@0", "hx"])
             if self.m0lane:
                 # the compares straight into their mask pairs (VOP3: the
                 # threshold from an SGPR), chain 1's 2.426265 test early (SP)
@@ -1558,10 +1575,12 @@ class Gen(object):
                 for k in range(2):
                     a(k, "v_cmp_gt_u32_e32 vcc, 0x3feb6000, {hx}\ns_mov_b64 %s, vcc"
                       % M[k], [], ["hx"])
-            a(1, "v_cmp_lt_u32_e32 vcc, 0x%x, v%d" % (BRANRED_HI - 1, self.VRED))
+            if not wide:
+                a(1, "v_cmp_lt_u32_e32 vcc, 0x%x, v%d" % (BRANRED_HI - 1, self.VRED))
             both("v_mov_b64_e32 {da}, 0", ["da"], [])
             a(0, "v_mov_b64_e32 {nn}, 0", ["nn"], [])
-            a(1, "s_cbranch_vccnz .Lslow_%s" % W)
+            if not wide:
+                a(1, "s_cbranch_vccnz .Lslow_%s" % W)
             # ---- fast path (no lane at or past 105414350): per chain, d = lanes
             # below 2.426265 and not small, e = the rest
             for k in range(2):
@@ -1602,6 +1621,8 @@ class Gen(object):
                     a(k, ".Lfe%s:" % lab)
                 else:
                     a(k, ".Lfe%s:\ns_mov_b64 exec, %s" % (lab, SV))
+            if wide:                     # (no lane is inf, nan or __branred's)
+                return
             if OOL:
                 a(1, "<OOL>")
             else:
@@ -1672,9 +1693,9 @@ class Gen(object):
                     for k in range(2):
                         a(k, "v_mov_b32_e32 %s, {x_hi}" % N[k], ["nn"],
                           ["x"] + (["nn"] if k else []))
-            both("v_mov_b64_e32 {da}, 0", ["da"], [])
-            if small:
+            if small:                    # (da = +-0 drops out of every term)
                 return
+            both("v_mov_b64_e32 {da}, 0", ["da"], [])
             # 0.85546875 as a double (0x3feb6000 : 0) in the free pair SP
             a(0, "s_mov_b32 %s, 0\ns_mov_b32 s%d, s%d" % (SC, self.SM0, SSAVE))
             for k in range(2):
@@ -1690,7 +1711,7 @@ class Gen(object):
                 a(k, lab + ":")
             a(1, "s_mov_b64 exec, %s" % SV)
 
-        if rng:
+        if known:
             ranges_known()
         else:
             ranges_general()
@@ -1701,8 +1722,9 @@ class Gen(object):
         if self.prio and self.prio_late and TRIG_DROP == "join":
             a(0, "s_setprio %d" % self.prio[1])
         a(0, "s_brev_b32 %s, 1" % SC)
-        both("v_bitop3_b32 {da_hi}, {da_hi}, {x_hi}, %s bitop3:0x78" % SC,
-             ["da"], ["x", "da"])
+        if not small:
+            both("v_bitop3_b32 {da_hi}, {da_hi}, {x_hi}, %s bitop3:0x78" % SC,
+                 ["da"], ["x", "da"])
         both("v_add_f64 {u}, |{x}|, @BIG@", ["u"], ["x"])
         both("v_add_f64 {q1}, {u}, -@BIG@", ["q1"], ["u"])
         both("v_lshlrev_b32_e32 {adr0}, 4, {u_lo}", ["adr0"], ["u"])
@@ -1715,16 +1737,21 @@ class Gen(object):
             if not small:
                 a(k, "s_mov_b64 exec, %s\ns_cbranch_execz %s" % (M[k], lab))
             a(k, "v_add_u32_e32 {adr0}, 0x%x, {adr0}" % S, ["adr0"], ["adr0"])
-            a(k, "v_add_f64 {xr}, {xr}, {da}", ["xr"], ["xr", "da"])
-            a(k, "v_mov_b64_e32 {da}, {xr}", ["da"], ["xr", "da"])
-            if not small:
+            if not small:                # (small: v = xr + (+-0) = xr, >= +0)
+                a(k, "v_add_f64 {xr}, {xr}, {da}", ["xr"], ["xr", "da"])
+                a(k, "v_mov_b64_e32 {da}, {xr}", ["da"], ["xr", "da"])
                 a(k, lab + ":")
         if not small:
             a(1, "s_mov_b64 exec, %s" % SV)
         both("v_mul_f64 {xx}, {xr}, {xr}", ["xx"], ["xr"])
         both("v_mul_f64 {m}, {xr}, {xx}", ["m"], ["xr", "xx"])
         both("v_fma_f64 {p}, {xx}, @SN5@, @SN3@", ["p"], ["xx"])
-        both("v_fma_f64 {s}, {m}, {p}, {da}", ["s"], ["m", "p", "da"])
+        if small and cos:                # (do_cos: s = v + v xx p with v = xr)
+            both("v_fma_f64 {s}, {m}, {p}, {xr}", ["s"], ["m", "p", "xr"])
+        elif small:                      # (do_sin: dx = +-0; + xr follows)
+            both("v_mul_f64 {s}, {m}, {p}", ["s"], ["m", "p"])
+        else:
+            both("v_fma_f64 {s}, {m}, {p}, {da}", ["s"], ["m", "p", "da"])
         both("v_fma_f64 {w}, {xx}, @CS6@, @CS4@", ["w"], ["xx"])
         both("v_fma_f64 {w}, {w}, {xx}, @CS2@", ["w"], ["w", "xx"])
         both("v_mul_f64 {w}, {w}, {xx}", ["w"], ["w", "xx"])
@@ -1749,6 +1776,10 @@ class Gen(object):
             if small:
                 if k:                    # (chain 0's 0.126 compare narrowed it)
                     a(k, "s_mov_b64 exec, %s" % SV)
+            elif midlo:
+                # (no TAYLOR_SIN lane: M[k] is not read again, the table
+                # result is every lane's)
+                a(k, "s_andn2_b64 exec, %s, %s\ns_cbranch_scc0 %s" % (SV, M[k], lab))
             elif self.salu:
                 # (no do_sin lanes — rare: M := SV out of line; the 0.126
                 # compare writes EXEC itself)
@@ -1760,10 +1791,16 @@ class Gen(object):
                 a(k, "s_andn2_b64 exec, %s, %s\ns_mov_b64 %s, %s\ns_cbranch_scc0 %s"
                   % (SV, M[k], M[k], SV, lab))
             a(k, "v_add_f64 {s}, {s}, {xr}", ["s"], ["s", "xr"])
-            a(k, "v_fma_f64 {w}, {da}, {xr}, {w}", ["w"], ["da", "xr", "w"])
-            if not rng or cos:
+            if not small:                # (small: dx xr = +-0, w >= +0)
+                a(k, "v_fma_f64 {w}, {da}, {xr}, {w}", ["w"], ["da", "xr", "w"])
+            if not known or cos:
                 a(k, "v_bitop3_b32 %s, %s, {x_hi}, %s bitop3:0x78" % (N[k], N[k], SC),
                   ["nn"], ["nn", "x"])
+            if midlo:
+                # a = (hp0 - |x|) + hp1 >= pi/2 - 1.44 > 0.126 in every do_sin
+                # lane (trig_ranges.h kMidLo): TAYLOR_SIN is never taken
+                a(k, lab + ":")
+                continue
             if self.salu:
                 a(k, "v_cmpx_gt_f64_e64 vcc, @C0126@, |{x}|\n"
                      "s_andn2_b64 %s, %s, exec\n"
@@ -1778,24 +1815,29 @@ class Gen(object):
             a(k, "v_fma_f64 {pt}, {pt}, {xx2}, @S3@", ["pt"], ["pt", "xx2"])
             a(k, "v_fma_f64 {pt}, {pt}, {xx2}, @S2@", ["pt"], ["pt", "xx2"])
             a(k, "v_fma_f64 {pt}, {pt}, {xx2}, @S1@", ["pt"], ["pt", "xx2"])
-            a(k, "v_mul_f64 {h}, {da}, 0.5", ["h"], ["da"])
-            a(k, "v_fma_f64 {q}, {pt}, |{x}|, -{h}", ["q"], ["pt", "x", "h"])
-            a(k, "v_fma_f64 {q}, {q}, {xx2}, {da}", ["q"], ["q", "xx2", "da"])
+            if small:                    # (dx = +-0: 0.5 dx and + dx drop out)
+                a(k, "v_mul_f64 {q}, {pt}, |{x}|", ["q"], ["pt", "x"])
+                a(k, "v_mul_f64 {q}, {q}, {xx2}", ["q"], ["q", "xx2"])
+            else:
+                a(k, "v_mul_f64 {h}, {da}, 0.5", ["h"], ["da"])
+                a(k, "v_fma_f64 {q}, {pt}, |{x}|, -{h}", ["q"], ["pt", "x", "h"])
+                a(k, "v_fma_f64 {q}, {q}, {xx2}, {da}", ["q"], ["q", "xx2", "da"])
             a(k, "v_add_f64 {x}, |{x}|, {q}", [], ["x", "q"])
             a(k, lab + ":")
         cs = small and cos               # (EXEC never left the handler's)
         a(1, "s_waitcnt lgkmcnt(0)" if cs else
           "s_mov_b64 exec, %s\ns_waitcnt lgkmcnt(0)" % SV)
+        allt = cs or midlo               # (the table result is every lane's)
         if self.prio and self.prio_late and TRIG_DROP == "wait":
             a(1, "s_setprio %d" % self.prio[1])
         both("v_fma_f64 {cor}, {s}, {TBb}, {TAa}", ["cor"], ["s", "EB", "EA"])
         both("v_fma_f64 {cor}, -{w}, {TA}, {cor}", ["cor"], ["w", "EA", "cor"])
         both("v_fma_f64 {cor}, {s}, {TB}, {cor}", ["cor"], ["s", "EB", "cor"])
         for k in range(2):
-            if not cs:
+            if not allt:
                 a(k, "s_mov_b64 exec, %s" % M[k])
             a(k, "v_add_f64 {x}, {TA}, {cor}", [], ["EA", "cor", "x"])
-        if not cs:
+        if not allt:
             a(1, "s_mov_b64 exec, %s" % SV)
         # the sign: n's bit 31 (negation xor a's sign for do_sin; cos small:
         # n = 0, do_cos's result as it is)
@@ -2475,10 +2517,12 @@ class Gen(object):
     # sin/cos (one translator layout): the host's range pass (trig_ranges.h)
     # picks them per node
     RANGE_HANDLERS = [("sin", "mid"), ("cos", "mid"), ("sin", "small"),
-                      ("cos", "small")]
+                      ("cos", "small"), ("cos", "midlo"), ("sin", "wide"),
+                      ("cos", "wide")]
 
     def range_handlers(self):
-        """SIN_MID, COS_MID, SIN_SMALL, COS_SMALL.  The exact cores with
+        """SIN_MID, COS_MID, SIN_SMALL, COS_SMALL, COS_MIDLO, SIN_WIDE,
+        COS_WIDE.  The exact cores with
         glibc_seq4's default scheme carry the specialised bodies
         (glibc_seq4(rng=...)); in every other core the ids alias the general
         handler: an entry of their own (every table offset is distinct and
@@ -2773,6 +2817,9 @@ class Gen(object):
                "H_COS_MID": ids.get("COS_MID", -1),
                "H_SIN_SMALL": ids.get("SIN_SMALL", -1),
                "H_COS_SMALL": ids.get("COS_SMALL", -1),
+               "H_COS_MIDLO": ids.get("COS_MIDLO", -1),
+               "H_SIN_WIDE": ids.get("SIN_WIDE", -1),
+               "H_COS_WIDE": ids.get("COS_WIDE", -1),
                "H_COUNT": len(names), "WINDOW": WINDOW,
                "SGPR_BASE": self.BASE,
                "LIM_HI": LIM_HI, "FAST_HI": FAST_HI}

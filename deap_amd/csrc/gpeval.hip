@@ -526,8 +526,9 @@ struct CoreIds {
       H_FAM_STRIDE, H_NEG, H_SIN, H_COS, H_COUNT;
   int H_NOT = -1, H_ITE0 = -1;      // the typed core only
   // [class][cos]: the sin/cos handler of a trig_ranges class (general, mid,
-  // small); the cores without specialised bodies alias SIN / COS there
-  int H_TRIG[3][2] = {{-1, -1}, {-1, -1}, {-1, -1}};
+  // small, midlo, wide; midlo is a cos class, its sin entry is SIN_MID); the
+  // cores without specialised bodies alias SIN / COS there
+  int H_TRIG[trig_ranges::kClasses][2] = {{-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}};
 };
 #define CORE_IDS(NS)                                                          \
   CoreIds {                                                                   \
@@ -536,17 +537,20 @@ struct CoreIds {
         NS::H_SIN, NS::H_COS, NS::H_COUNT, -1, -1,                             \
     {                                                                         \
       {NS::H_SIN, NS::H_COS}, {NS::H_SIN_MID, NS::H_COS_MID},                 \
-          {NS::H_SIN_SMALL, NS::H_COS_SMALL}                                  \
+          {NS::H_SIN_SMALL, NS::H_COS_SMALL}, {NS::H_SIN_MID, NS::H_COS_MIDLO}, \
+          {NS::H_SIN_WIDE, NS::H_COS_WIDE}                                    \
     }                                                                         \
   }
 static_assert(asmcore::H_SIN_MID == asmcore::H_COS + 1 &&
-                  asmcore::H_COS_SMALL == asmcore::H_COUNT - 1 &&
+                  asmcore::H_COS_SMALL == asmcore::H_COS + 4 &&
+                  asmcore::H_COS_MIDLO == asmcore::H_COS + 5 &&
+                  asmcore::H_COS_WIDE == asmcore::H_COUNT - 1 &&
                   asmcore_exact::H_SIN_MID == asmcore::H_SIN_MID &&
-                  asmcore_exact::H_COS_SMALL == asmcore::H_COS_SMALL &&
+                  asmcore_exact::H_COS_WIDE == asmcore::H_COS_WIDE &&
                   asmcore_exact_deep::H_SIN_MID == asmcore_deep::H_SIN_MID &&
-                  asmcore_exact_deep::H_COS_SMALL == asmcore_deep::H_COS_SMALL &&
-                  asmcore32::H_COS_SMALL == asmcore::H_COS_SMALL &&
-                  asmcore32_deep::H_COS_SMALL == asmcore_deep::H_COS_SMALL,
+                  asmcore_exact_deep::H_COS_WIDE == asmcore_deep::H_COS_WIDE &&
+                  asmcore32::H_COS_WIDE == asmcore::H_COS_WIDE &&
+                  asmcore32_deep::H_COS_WIDE == asmcore_deep::H_COS_WIDE,
               "the range-specialised sin/cos ids follow COS in every core's layout");
 constexpr CoreIds kIds = CORE_IDS(asmcore);
 constexpr CoreIds kIdsDeep = CORE_IDS(asmcore_deep);
@@ -558,6 +562,8 @@ constexpr CoreIds kIdsTyped = [] {
   return c;                              // (no sin/cos: H_TRIG stays -1)
 }();
 static_assert(asmcore_typed::WINDOW == asmcore::WINDOW, "one window size");
+static_assert(32 + (3 + trig_ranges::kClasses) * 8 <= 128,
+              "translate_device's pinned header holds the class counts");
 static_assert(asmcore32::H_COUNT == asmcore::H_COUNT &&
                   asmcore32_deep::H_COUNT == asmcore_deep::H_COUNT &&
                   asmcore32_deep::H_BIN0 == asmcore_deep::H_BIN0 &&
@@ -629,18 +635,23 @@ __global__ __launch_bounds__(256) void const_hits(const uint32_t* kc, int64_t n,
 // the host (gpe_debug_translate, tests) and in translate_kernel.
 // `bnd` (the exact cores, while writing): the case columns' (lo, hi), nb of
 // them — every sin/cos word is then the handler of its argument's proven
-// range (trig_ranges.h), counted per class into `cls3` when given; null:
-// every sin/cos is the general handler.  The word count is the same.
+// range (trig_ranges.h; `mode`: kBase or kAll), counted into `cls` when given
+// (kTrigCounts words: the base classes general, mid, small, then the words
+// per class picked); null: every sin/cos is the general handler.  The word
+// count is the same.
+constexpr int kTrigCounts = 3 + trig_ranges::kClasses;
+static_assert(sizeof(gpe_ctx::trig_classes) == kTrigCounts * sizeof(int64_t),
+              "ctx.h holds the class counts");
 HD int64_t translate_words(const uint32_t* w, const uint32_t* tab, const CoreIds& I,
                            bool f32, int window_use, uint32_t* out,
                            const double* bnd = nullptr, int nb = 0,
-                           uint32_t* cls3 = nullptr) {
+                           uint32_t* cls = nullptr, int mode = trig_ranges::kBase) {
   constexpr int WINDOW = asmcore::WINDOW;
   const int D = I.D, NV = I.NV;
   int64_t n = 0;
   int pos = 0;
   const bool ranges = bnd != nullptr && out != nullptr;
-  trig_ranges::Walk R(bnd, ranges ? nb : 0);
+  trig_ranges::Walk R(bnd, ranges ? nb : 0, mode);
   auto emit = [&](uint32_t v) {
     if (out) out[n] = v;
     ++n;
@@ -691,10 +702,14 @@ HD int64_t translate_words(const uint32_t* w, const uint32_t* tab, const CoreIds
       const int c = R.step(word, konst ? w[0] : 0u, konst ? w[1] : 0u);
       if (c >= 0) {
         h = I.H_TRIG[c][op == OP_COS ? 1 : 0];
-        if (cls3) ++cls3[c];
+        if (cls) {
+          ++cls[R.base];
+          ++cls[3 + c];
+        }
       }
-    } else if (cls3 && out && (op == OP_SIN || op == OP_COS)) {
-      ++cls3[0];                              // (no bounds: all general)
+    } else if (cls && out && (op == OP_SIN || op == OP_COS)) {
+      ++cls[0];                               // (no bounds: all general)
+      ++cls[3];
     }
     const int need = konst ? 3 : 1;
     if (pos + need > window_use) {            // next word would leave it
@@ -729,11 +744,13 @@ int window_use() {
 
 void translate_program(const uint32_t* w, const std::vector<uint32_t>& tab,
                        std::vector<uint32_t>& out, bool f32 = false,
-                       const CoreIds& I = kIds, const double* bnd = nullptr, int nb = 0) {
+                       const CoreIds& I = kIds, const double* bnd = nullptr, int nb = 0,
+                       int mode = trig_ranges::kBase) {
   const int64_t n = translate_words(w, tab.data(), I, f32, window_use(), nullptr);
   const size_t base = out.size();
   out.resize(base + (size_t)n);
-  translate_words(w, tab.data(), I, f32, window_use(), out.data() + base, bnd, nb);
+  translate_words(w, tab.data(), I, f32, window_use(), out.data() + base, bnd, nb, nullptr,
+                  mode);
 }
 
 // Device translation (translate_device): per program, its core class
@@ -747,7 +764,7 @@ __global__ __launch_bounds__(256) void translate_kernel(
     const uint32_t* code, const int64_t* off, const uint8_t* cls, int64_t n,
     XlateTabs T, int f32, int wuse, int pass, uint32_t* len, const uint32_t* start,
     uint32_t* out, uint8_t* typed_ok, const double* bnd, int nb,
-    unsigned long long* trig_cls) {
+    unsigned long long* trig_cls, int trig_mode) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t* w = code + off[i];
@@ -776,10 +793,11 @@ __global__ __launch_bounds__(256) void translate_kernel(
   else if (!trig_cls)
     translate_words(w, T.tab[t], T.ids[t], f32 != 0, wuse, out + start[i]);
   else {
-    uint32_t c3[3] = {0, 0, 0};
-    translate_words(w, T.tab[t], T.ids[t], f32 != 0, wuse, out + start[i], bnd, nb, c3);
-    for (int k = 0; k < 3; ++k)
-      if (c3[k]) atomicAdd(trig_cls + k, (unsigned long long)c3[k]);
+    uint32_t cn[kTrigCounts] = {};
+    translate_words(w, T.tab[t], T.ids[t], f32 != 0, wuse, out + start[i], bnd, nb, cn,
+                    trig_mode);
+    for (int k = 0; k < kTrigCounts; ++k)
+      if (cn[k]) atomicAdd(trig_cls + k, (unsigned long long)cn[k]);
   }
 }
 
@@ -819,7 +837,7 @@ int translate_device(gpe_ctx* ctx, const std::vector<uint8_t>* cls, const XlateT
   HIPCHK(hipMemsetAsync(ctx->d_xl_len + n, 0, sizeof(uint32_t), ctx->stream));
   hipLaunchKernelGGL(translate_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->d_code,
                      ctx->d_off, d_cls, n, T, f32 ? 1 : 0, window_use(), 0, ctx->d_xl_len,
-                     nullptr, nullptr, d_typed, nullptr, 0, nullptr);
+                     nullptr, nullptr, d_typed, nullptr, 0, nullptr, 0);
   HIPCHK(hipGetLastError());
   if (ctx->diag) {
     HIPCHK(hipEventRecord(ctx->ev_redo[1], ctx->stream));
@@ -843,17 +861,17 @@ int translate_device(gpe_ctx* ctx, const std::vector<uint8_t>* cls, const XlateT
   HIPCHK(hipcub::DeviceScan::ExclusiveSum(ctx->d_sort_tmp, tmp_bytes, ctx->d_xl_len, *d_start,
                                           (int)(n + 1), ctx->stream));
   xlap("scan");
-  char* pin = pinned(ctx, 64 + (size_t)n);
+  char* pin = pinned(ctx, 128 + (size_t)n);      // (a 128-byte header, then typed_ok)
   if (!pin) return fail(ctx, GPE_E_HIP, "hipHostMalloc (translation)");
   xlap("pinned");
   HIPCHK(hipMemcpyAsync(pin, *d_start + n, sizeof(uint32_t), hipMemcpyDeviceToHost,
                         ctx->stream));
   if (typed)
-    HIPCHK(hipMemcpyAsync(pin + 64, d_typed, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(pin + 128, d_typed, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   uint32_t total = 0;
   std::memcpy(&total, pin, sizeof(uint32_t));
-  if (typed) ctx->typed_ok.assign((const uint8_t*)pin + 64, (const uint8_t*)pin + 64 + n);
+  if (typed) ctx->typed_ok.assign((const uint8_t*)pin + 128, (const uint8_t*)pin + 128 + n);
   if (ctx->diag)
     fprintf(stderr, "translate_device lengths+scan %.3f ms\n",
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_x0)
@@ -861,20 +879,21 @@ int translate_device(gpe_ctx* ctx, const std::vector<uint8_t>* cls, const XlateT
   const size_t words = (size_t)total + 2 * asmcore::WINDOW;   // s_load_dwordx16 slack
   if (ensure(ctx, d_out, out_cap, words)) return GPE_E_HIP;
   const bool use_bnd = ranges && ctx->trig_ranges && ctx->d_col_bnd && ctx->d_trig_cls;
-  if (ranges) ctx->trig_classes[0] = ctx->trig_classes[1] = ctx->trig_classes[2] = 0;
+  if (ranges) std::fill(ctx->trig_classes, ctx->trig_classes + kTrigCounts, (int64_t)0);
   if (ranges && ctx->d_trig_cls)
-    HIPCHK(hipMemsetAsync(ctx->d_trig_cls, 0, 3 * sizeof(unsigned long long), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_trig_cls, 0, kTrigCounts * sizeof(unsigned long long),
+                          ctx->stream));
   // (with the switch off the classes are still counted: all general)
   hipLaunchKernelGGL(translate_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->d_code,
                      ctx->d_off, d_cls, n, T, f32 ? 1 : 0, window_use(), 1, ctx->d_xl_len,
                      *d_start, *d_out, d_typed,
                      use_bnd ? (const double*)ctx->d_col_bnd : nullptr, ctx->nv,
-                     ranges ? ctx->d_trig_cls : nullptr);
+                     ranges ? ctx->d_trig_cls : nullptr, ctx->trig_ranges);
   HIPCHK(hipGetLastError());
-  // the class counts ride in the pinned header (bytes 32..55; the total was
+  // the class counts ride in the pinned header (bytes 32..95; the total was
   // read above) and are read after this function's last synchronisation
   if (ranges && ctx->d_trig_cls)
-    HIPCHK(hipMemcpyAsync(pin + 32, ctx->d_trig_cls, 3 * sizeof(unsigned long long),
+    HIPCHK(hipMemcpyAsync(pin + 32, ctx->d_trig_cls, kTrigCounts * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost, ctx->stream));
   const uint32_t end_word = T.tab[typed ? 2 : 0][T.ids[typed ? 2 : 0].H_END];
   std::vector<uint32_t> slack(2 * asmcore::WINDOW, end_word);
@@ -882,9 +901,9 @@ int translate_device(gpe_ctx* ctx, const std::vector<uint8_t>* cls, const XlateT
                         hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (ranges && ctx->d_trig_cls) {
-    unsigned long long c3[3];
-    std::memcpy(c3, pin + 32, sizeof(c3));
-    for (int k = 0; k < 3; ++k) ctx->trig_classes[k] = (int64_t)c3[k];
+    unsigned long long cn[kTrigCounts];
+    std::memcpy(cn, pin + 32, sizeof(cn));
+    for (int k = 0; k < kTrigCounts; ++k) ctx->trig_classes[k] = (int64_t)cn[k];
   }
   return 0;
 }
@@ -1627,7 +1646,9 @@ int gpe_create(int device, gpe_ctx** out) {
     ctx->div_w = atoi(env);
   if ((env = getenv("GPE_DIAG"))) ctx->diag = atoi(env);
   if ((env = getenv("GPE_EXACT_ALL"))) ctx->exact_all = atoi(env) != 0;
-  if ((env = getenv("GPE_TRIG_RANGES"))) ctx->trig_ranges = atoi(env) != 0;
+  if ((env = getenv("GPE_TRIG_RANGES")))
+    ctx->trig_ranges = atoi(env) <= 0 ? trig_ranges::kOff
+                       : atoi(env) == 1 ? trig_ranges::kBase : trig_ranges::kAll;
   if ((env = getenv("GPE_REDO_EXP")) && atoi(env) >= 14 && atoi(env) <= 40)
     ctx->redo_hi = (uint32_t)(0x3ff + atoi(env)) << 20;
   if ((env = getenv("GPE_REDO_EXP_DEEP")) && atoi(env) >= 14 && atoi(env) <= 40)
@@ -1780,7 +1801,7 @@ int gpe_set_cases(gpe_ctx* ctx, int machine, const void* X, int n_vars,
   if (ctx->d_col_bnd) HIPCHK(hipFree(ctx->d_col_bnd));
   ctx->d_col_bnd = nullptr;
   ctx->col_bnd.clear();
-  ctx->trig_classes[0] = ctx->trig_classes[1] = ctx->trig_classes[2] = 0;
+  std::fill(ctx->trig_classes, ctx->trig_classes + kTrigCounts, (int64_t)0);
   size_t xb, tb;
   if (machine == GPE_MACHINE_F) {
     ctx->nt = n_terms;
@@ -1839,7 +1860,7 @@ int gpe_set_cases(gpe_ctx* ctx, int machine, const void* X, int n_vars,
     HIPCHK(hipMemcpy(ctx->d_col_bnd, B.data(), B.size() * sizeof(double),
                      hipMemcpyHostToDevice));
     if (!ctx->d_trig_cls)
-      HIPCHK(hipMalloc((void**)&ctx->d_trig_cls, 3 * sizeof(unsigned long long)));
+      HIPCHK(hipMalloc((void**)&ctx->d_trig_cls, kTrigCounts * sizeof(unsigned long long)));
   }
   // the first target column's truths (HITS_BOOL: a constant program's hits)
   ctx->label_true = 0;
@@ -3365,7 +3386,18 @@ int gpe_debug_translate_ranges(const uint32_t* code, int64_t n_words,
                                int n_table, uint32_t* out, int64_t out_cap,
                                int64_t* starts, int64_t* n_out, const double* lo,
                                const double* hi) {
+  return gpe_debug_translate_mode(code, n_words, off, n_prog, depth, nv, table, n_table,
+                                     out, out_cap, starts, n_out, lo, hi, trig_ranges::kBase);
+}
+
+int gpe_debug_translate_mode(const uint32_t* code, int64_t n_words,
+                                const int64_t* off, int64_t n_prog,
+                                const int32_t* depth, int nv, const uint32_t* table,
+                                int n_table, uint32_t* out, int64_t out_cap,
+                                int64_t* starts, int64_t* n_out, const double* lo,
+                                const double* hi, int mode) {
   if ((lo == nullptr) != (hi == nullptr)) return GPE_E_INVALID;
+  if (mode != trig_ranges::kBase && mode != trig_ranges::kAll) return GPE_E_INVALID;
   std::vector<double> bnd;
   if (lo)
     for (int v = 0; v < nv; ++v) {
@@ -3389,7 +3421,7 @@ int gpe_debug_translate_ranges(const uint32_t* code, int64_t n_words,
     if (!ok || (!deep_core && depth[i] > asmcore::D)) continue;
     starts[i] = (int64_t)acode.size();
     translate_program(code + off[i], tab, acode, false, deep_core ? kIdsDeep : kIds,
-                      lo ? bnd.data() : nullptr, nv);
+                      lo ? bnd.data() : nullptr, nv, mode);
   }
   if ((int64_t)acode.size() > out_cap) return GPE_E_INVALID;
   std::copy(acode.begin(), acode.end(), out);
@@ -3399,14 +3431,20 @@ int gpe_debug_translate_ranges(const uint32_t* code, int64_t n_words,
 
 int gpe_debug_trig_classes(const uint32_t* code, int64_t n_words, const double* lo,
                            const double* hi, int nv, int32_t* out, int64_t cap) {
-  if (!code || n_words <= 0 || nv < 0 || (nv && (!lo || !hi)) || (cap && !out) || cap < 0)
+  return gpe_debug_trig_classes_mode(code, n_words, lo, hi, nv, trig_ranges::kBase, out, cap);
+}
+
+int gpe_debug_trig_classes_mode(const uint32_t* code, int64_t n_words, const double* lo,
+                            const double* hi, int nv, int mode, int32_t* out, int64_t cap) {
+  if (!code || n_words <= 0 || nv < 0 || (nv && (!lo || !hi)) || (cap && !out) || cap < 0 ||
+      (mode != trig_ranges::kBase && mode != trig_ranges::kAll))
     return -1;
   std::vector<double> bnd;
   for (int v = 0; v < nv; ++v) {
     bnd.push_back(lo[v]);
     bnd.push_back(hi[v]);
   }
-  trig_ranges::Walk R(bnd.data(), nv);
+  trig_ranges::Walk R(bnd.data(), nv, mode);
   int64_t n = 0;
   for (int64_t i = 0; i < n_words;) {
     const uint32_t w = code[i], op = w & 0xffu;
@@ -3428,6 +3466,12 @@ int gpe_debug_trig_classes(const uint32_t* code, int64_t n_words, const double* 
 int gpe_last_trig_classes(const gpe_ctx* ctx, int64_t* out) {
   if (!ctx || !out) return GPE_E_INVALID;
   for (int k = 0; k < 3; ++k) out[k] = ctx->trig_classes[k];
+  return 0;
+}
+
+int gpe_last_trig_picked(const gpe_ctx* ctx, int64_t* out) {
+  if (!ctx || !out) return GPE_E_INVALID;
+  for (int k = 0; k < trig_ranges::kClasses; ++k) out[k] = ctx->trig_classes[3 + k];
   return 0;
 }
 

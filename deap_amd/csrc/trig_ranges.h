@@ -2,18 +2,51 @@
 // argument of a program provably falls in, from the [min, max] of the case
 // columns (gpe_set_cases).  Plain interval arithmetic along the postfix
 // words, run by translate_words (host and device) while it emits a program
-// for the exact cores, whose SIN_MID / COS_MID / SIN_SMALL / COS_SMALL
-// handlers (gen_asm.py glibc_seq4(rng=...)) run glibc's operations for that
-// range without the tests that find it.
+// for the exact cores, whose SIN_MID / COS_MID / SIN_SMALL / COS_SMALL /
+// COS_MIDLO / SIN_WIDE / COS_WIDE handlers (gen_asm.py glibc_seq4(rng=...))
+// run glibc's operations for that range without the tests that find it.
 //
 // The invariant the handlers rest on: a value that reaches a specialised
 // handler is inside its range in EVERY lane — the pad lanes of a partial
 // last tile (f_stage pads with 0.0: every column's bounds are hulled with
 // 0.0 by the caller) and the lanes of a program that has already flagged an
-// error elsewhere.  Hence the taint rule: a value that may be inf or nan in
-// any lane (a division whose denominator may be 0, an unbounded column, a
-// non-finite constant, a bound past 1e300) is "tainted", every result
-// computed from it is tainted, and a tainted argument is class general.
+// error elsewhere — or (MID, SMALL, MIDLO only) is a NaN whose program and
+// tile are already handed to the C++ pass (below).  Hence the taint rule: a
+// value that may be inf or nan in any lane (a division whose denominator may
+// be 0, an unbounded column, a non-finite constant, a bound past 1e300) is
+// "tainted", every arithmetic result computed from it is tainted, and a
+// tainted argument is class general.
+//
+// The third state, "nanable" (kAll only): every lane is finite and inside the
+// bounds, or NaN.  sin/cos of a tainted argument is nanable within [-1, 1]:
+// the general handler returns glibc's value for a finite lane and NaN for an
+// inf or nan one (x - x).  The state is closed under add, sub, mul, neg
+// (a NaN operand gives NaN; finite operands inside their bounds give a
+// result inside the hull, as for clean values), under protectedDiv while the
+// denominator's interval excludes 0 (a NaN denominator is not == 0, the
+// quotient is NaN; the numpy variant turns that NaN into 1.0, so its hull
+// includes 1.0), and is tainted again by a denominator that may be 0 and by
+// a bound past kHuge.  A nanable argument may take MID, SMALL and MIDLO, not
+// WIDE (kept for clean values: its body drops the VRED update).
+//   Why a NaN lane may run a specialised handler.  (1) Whatever it computes
+// is discarded: NaN lanes are born only where a value turns nanable, in an
+// inner sin/cos of the same program whose argument was tainted (the closed
+// operations only pass a NaN on: their finite lanes stay inside the hull,
+// below kHuge).  That node is class general, its lane held an inf or a nan,
+// and the general handler has put |x|.hi >= 0x7ff00000 into VRED; END then
+// leaves to the C++ `finish`, which hands that (program, tile) to
+// f_eval_pairs.  (2) It is safe: the handlers' only memory accesses are the
+// two table gathers at (u.lo << 4) + {0, S, 2 S}, u = |x| + BIG, and every
+// NaN in the machine has a zero low word, which v_add_f64 keeps, so a NaN
+// lane gathers entry 0: gpe_set_cases canonicalises the cases' NaNs to the
+// default NaN (canon_nan), non-finite constants are tainted and so are the
+// values computed from them up to the general handler that makes x - x, the
+// default NaN (0x7ff8000000000000); every fp64 op propagates an operand's
+// NaN (quieted, low word kept) or makes the default one; and the handlers'
+// sign operations touch high words only.  The compares are false for NaN
+// (the lane runs the d block and the table path, fp64 arithmetic only), and
+// every path restores EXEC (gen_asm.py check_exec).  Both are executed in
+// tests/test_asm_emu_ranges_more.py.
 //
 // Soundness of the bounds: add, sub, mul, div and neg are correctly rounded
 // and therefore monotone in each operand, so the same round-to-nearest fp64
@@ -33,11 +66,21 @@
 
 namespace trig_ranges {
 
-enum Class { GENERAL = 0, MID = 1, SMALL = 2 };
+// GENERAL, MID, SMALL: the base classes (kBase picks only these); MIDLO (cos
+// only) and WIDE: kAll's.  The numbering is the ABI's (gpe_last_trig_classes)
+enum Class { GENERAL = 0, MID = 1, SMALL = 2, MIDLO = 3, WIDE = 4, kClasses = 5 };
+// GPE_TRIG_RANGES: 0 general handlers only (no pass), 1 the base classes, 2 all
+enum Mode { kOff = 0, kBase = 1, kAll = 2 };
 constexpr int kSlots = 12;              // operand-stack slots (the deep cores' D)
 // class thresholds on m = max(|lo|, |hi|): deliberately below glibc's own
 // (|x| < 0.85546875: hx < 0x3feb6000; |x| < 2.426265...: hx < 0x400368fd)
 constexpr double kSmall = 0.855, kMid = 2.42;
+// cos, |x| < kMidLo: the do_sin lanes (0.85546875 <= |x|) have the argument
+// a = (hp0 - |x|) + hp1 > pi/2 - 1.44 = 0.13080 > 0.126, TAYLOR_SIN's bound:
+// a margin of 0.0048, against two roundings of 2^-53 relative
+constexpr double kMidLo = 1.44;
+// |x| < kWide, clean: below __branred's 105414350 (hx < 0x419921fb) by 5 %
+constexpr double kWide = 1e8;
 constexpr double kHuge = 1e300;         // a bound past it: tainted
 
 // opcodes of the flattener words this pass reads (lower_core.h / gpeval.hip)
@@ -47,49 +90,71 @@ enum : uint32_t {
   W_LT = 26, W_NEG = 48, W_SIN = 49, W_COS = 50, W_NPDIV = 56, W_RNPDIV = 59
 };
 
+enum State : uint8_t { TAINT = 0, CLEAN = 1, NANABLE = 2 };
+
 struct Iv {
   double lo, hi;
-  bool ok;                              // false: tainted (may be inf / nan)
+  State st;                             // TAINT: may be inf / nan / anything
 };
 
 TR_HD inline double absd(double v) { return v < 0 ? -v : v; }
 TR_HD inline double mind(double a, double b) { return a < b ? a : b; }
 TR_HD inline double maxd(double a, double b) { return a > b ? a : b; }
-TR_HD inline Iv taint() { return Iv{0.0, 0.0, false}; }
+TR_HD inline Iv taint() { return Iv{0.0, 0.0, TAINT}; }
 // (the comparisons are false for nan: tainted)
-TR_HD inline Iv mk(double lo, double hi) {
-  const bool ok = lo <= hi && lo >= -kHuge && hi <= kHuge;
-  return ok ? Iv{lo, hi, true} : taint();
+TR_HD inline Iv mk(double lo, double hi, State st = CLEAN) {
+  const bool ok = st != TAINT && lo <= hi && lo >= -kHuge && hi <= kHuge;
+  return ok ? Iv{lo, hi, st} : taint();
+}
+// both clean: clean; a tainted one: tainted; else nanable
+TR_HD inline State join(const Iv& a, const Iv& b) {
+  return a.st == TAINT || b.st == TAINT ? TAINT
+         : a.st == CLEAN && b.st == CLEAN ? CLEAN : NANABLE;
 }
 TR_HD inline Iv point(double c) { return mk(c, c); }
 TR_HD inline Iv add(const Iv& a, const Iv& b) {
-  return a.ok && b.ok ? mk(a.lo + b.lo, a.hi + b.hi) : taint();
+  return mk(a.lo + b.lo, a.hi + b.hi, join(a, b));
 }
 TR_HD inline Iv sub(const Iv& a, const Iv& b) {       // a - b
-  return a.ok && b.ok ? mk(a.lo - b.hi, a.hi - b.lo) : taint();
+  return mk(a.lo - b.hi, a.hi - b.lo, join(a, b));
 }
-TR_HD inline Iv neg(const Iv& a) { return a.ok ? mk(-a.hi, -a.lo) : taint(); }
-TR_HD inline Iv hull4(double p, double q, double r, double s) {
-  return mk(mind(mind(p, q), mind(r, s)), maxd(maxd(p, q), maxd(r, s)));
+TR_HD inline Iv neg(const Iv& a) { return mk(-a.hi, -a.lo, a.st); }
+TR_HD inline Iv hull4(double p, double q, double r, double s, State st) {
+  return mk(mind(mind(p, q), mind(r, s)), maxd(maxd(p, q), maxd(r, s)), st);
 }
 TR_HD inline Iv mul(const Iv& a, const Iv& b) {
-  if (!a.ok || !b.ok) return taint();
-  return hull4(a.lo * b.lo, a.lo * b.hi, a.hi * b.lo, a.hi * b.hi);
+  const State st = join(a, b);
+  if (st == TAINT) return taint();
+  return hull4(a.lo * b.lo, a.lo * b.hi, a.hi * b.lo, a.hi * b.hi, st);
 }
 // protectedDiv(num, den): den == 0 ? 1.0 : num / den.  The numpy variant
 // (inf / nan -> 1.0) agrees wherever the quotient is finite, which the bound
-// check of hull4 guarantees; where it is not, both are tainted here.
-TR_HD inline Iv pdiv(const Iv& n, const Iv& d) {
-  if (!n.ok || !d.ok) return taint();
-  if (d.lo == 0.0 && d.hi == 0.0) return point(1.0);
+// check of hull4 guarantees; where it is not, both are tainted here.  A
+// nanable operand: the quotient of a NaN lane is NaN (the numpy variant:
+// 1.0, hulled in); a denominator that may be 0 taints, the exact 0 too.
+TR_HD inline Iv pdiv(const Iv& n, const Iv& d, bool np) {
+  const State st = join(n, d);
+  if (st == TAINT) return taint();
+  if (st == CLEAN && d.lo == 0.0 && d.hi == 0.0) return point(1.0);
   if (d.lo <= 0.0 && d.hi >= 0.0) return taint();    // may divide by ~0: +-inf
-  return hull4(n.lo / d.lo, n.lo / d.hi, n.hi / d.lo, n.hi / d.hi);
+  const Iv q = hull4(n.lo / d.lo, n.lo / d.hi, n.hi / d.lo, n.hi / d.hi, st);
+  if (q.st == NANABLE && np) return mk(mind(q.lo, 1.0), maxd(q.hi, 1.0), NANABLE);
+  return q;
 }
 
-TR_HD inline int classify(const Iv& a) {
-  if (!a.ok) return GENERAL;
+// The class of a sin (cos) node from its argument; `mode` kBase or kAll.
+TR_HD inline int classify(const Iv& a, bool cos, int mode) {
+  if (a.st == TAINT) return GENERAL;
   const double m = maxd(absd(a.lo), absd(a.hi));
-  return m < kSmall ? SMALL : m < kMid ? MID : GENERAL;
+  if (m < kSmall) return SMALL;
+  if (mode == kAll && cos && m < kMidLo) return MIDLO;
+  if (m < kMid) return MID;
+  return mode == kAll && a.st == CLEAN && m < kWide ? WIDE : GENERAL;
+}
+// The class kBase gives the same node (a value is clean exactly when kBase
+// calls it untainted, with the same bounds: nanable values never turn clean)
+TR_HD inline int base_class(const Iv& a) {
+  return a.st == CLEAN ? classify(a, false, kBase) : GENERAL;
 }
 
 // Upper bound of glibc's sin(t) for 0 <= t <= 1.5: the Taylor polynomial
@@ -103,21 +168,23 @@ TR_HD inline double sin_ub(double t) {
   const double p = t - t * t2 * (1.0 / 6.0) + t * t2 * t2 * (1.0 / 120.0);
   return mind(1.0, p * (1.0 + 0x1p-40));
 }
-TR_HD inline Iv sin_iv(const Iv& a) {
-  if (!a.ok) return taint();
-  if (a.lo < -1.5 || a.hi > 1.5) return mk(-1.0, 1.0);
+// (a tainted argument, kAll: finite lanes give a value in [-1, 1], inf and
+// nan lanes NaN — nanable; kBase: tainted)
+TR_HD inline Iv sin_iv(const Iv& a, int mode) {
+  if (a.st == TAINT) return mode == kAll ? mk(-1.0, 1.0, NANABLE) : taint();
+  if (a.lo < -1.5 || a.hi > 1.5) return mk(-1.0, 1.0, a.st);
   // on [-1.5, 1.5] sin is odd and has the sign of its argument (glibc's
   // too: it computes sin |x| and restores the sign)
-  return mk(a.lo < 0.0 ? -sin_ub(-a.lo) : 0.0, a.hi > 0.0 ? sin_ub(a.hi) : 0.0);
+  return mk(a.lo < 0.0 ? -sin_ub(-a.lo) : 0.0, a.hi > 0.0 ? sin_ub(a.hi) : 0.0, a.st);
 }
 // Lower bound of glibc's cos for |x| <= m <= 1.25: cos x >= 1 - x^2/2 >=
 // 1 - m^2/2 (>= 0.21 there); narrowed by a relative 2^-40 for glibc's ulp
 // and this evaluation's roundings, as above.
-TR_HD inline Iv cos_iv(const Iv& a) {
-  if (!a.ok) return taint();
+TR_HD inline Iv cos_iv(const Iv& a, int mode) {
+  if (a.st == TAINT) return mode == kAll ? mk(-1.0, 1.0, NANABLE) : taint();
   const double m = maxd(absd(a.lo), absd(a.hi));
-  if (m > 1.25) return mk(-1.0, 1.0);
-  return mk((1.0 - m * m * 0.5) * (1.0 - 0x1p-40), 1.0);
+  if (m > 1.25) return mk(-1.0, 1.0, a.st);
+  return mk((1.0 - m * m * 0.5) * (1.0 - 0x1p-40), 1.0, a.st);
 }
 
 // The walk: T and the stack slots' intervals.  `bnd` holds (lo, hi) per
@@ -125,10 +192,13 @@ TR_HD inline Iv cos_iv(const Iv& a) {
 struct Walk {
   const double* bnd;
   int nb;
+  int mode;
+  int base;                             // base_class of the last sin/cos node
   Iv T;
   Iv S[kSlots];
 
-  TR_HD Walk(const double* b, int n) : bnd(b), nb(n), T(taint()) {
+  TR_HD Walk(const double* b, int n, int m = kBase)
+      : bnd(b), nb(n), mode(m), base(GENERAL), T(taint()) {
     for (int i = 0; i < kSlots; ++i) S[i] = taint();
   }
   TR_HD Iv var(uint32_t x) const {
@@ -139,8 +209,8 @@ struct Walk {
     if (d < (uint32_t)kSlots) S[d] = T;
   }
   // One instruction word (c0, c1: the two words after it, read only when the
-  // op takes an inline constant).  Returns the class of a sin/cos node, -1
-  // for any other op.
+  // op takes an inline constant).  Returns the class of a sin/cos node (and
+  // sets `base`), -1 for any other op.
   TR_HD int step(uint32_t word, uint32_t c0, uint32_t c1) {
     const uint32_t op = word & 0xffu, d = (word >> 8) & 0xffu, x = word >> 16;
     const Iv K = point(__builtin_bit_cast(double, (uint64_t)c0 | ((uint64_t)c1 << 32)));
@@ -159,8 +229,9 @@ struct Walk {
     } else if (op == W_NEG) {
       T = neg(T);
     } else if (op == W_SIN || op == W_COS) {
-      const int c = classify(T);
-      T = op == W_SIN ? sin_iv(T) : cos_iv(T);
+      const int c = classify(T, op == W_COS, mode);
+      base = base_class(T);
+      T = op == W_SIN ? sin_iv(T, mode) : cos_iv(T, mode);
       return c;
     } else if ((op >= W_ADD && op < W_LT) || (op >= W_NPDIV && op < W_NPDIV + 6)) {
       // T = fam(a, T): add, sub (a - T), rsub (T - a), mul, div
@@ -170,7 +241,7 @@ struct Walk {
       const int form = np ? (int)(op - W_NPDIV) % 3 : (int)(op - W_ADD) % 3;
       const Iv a = form == 0 ? slot(d) : form == 1 ? var(x) : K;
       T = fam == 0 ? add(a, T) : fam == 1 ? sub(a, T) : fam == 2 ? sub(T, a)
-          : fam == 3 ? mul(a, T) : fam == 4 ? pdiv(a, T) : pdiv(T, a);
+          : fam == 3 ? mul(a, T) : fam == 4 ? pdiv(a, T, np) : pdiv(T, a, np);
     } else {
       T = taint();                      // an op this pass does not model
     }

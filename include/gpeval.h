@@ -425,11 +425,38 @@ int gpe_debug_translate_ranges(const uint32_t* code, int64_t n_words,
 int gpe_debug_trig_classes(const uint32_t* code, int64_t n_words, const double* lo,
                            const double* hi, int nv, int32_t* out, int64_t cap);
 
-/* The sin/cos words of the last exact-core translation per class: out[0]
- * general, out[1] mid, out[2] small handlers (GPE_TRIG_RANGES=0, read once
- * by gpe_create: all general).  The column bounds the classes are proven
- * from are those of the last gpe_set_cases. */
+/* The sin/cos words of the last exact-core translation per base class:
+ * out[0] general, out[1] mid, out[2] small, as gpe_debug_trig_classes
+ * classes them (GPE_TRIG_RANGES=0, read once by gpe_create: all general).
+ * The column bounds the classes are proven from are those of the last
+ * gpe_set_cases.  The handlers picked: gpe_last_trig_picked. */
 int gpe_last_trig_classes(const gpe_ctx* ctx, int64_t* out);
+
+/* gpe_debug_translate_ranges and gpe_debug_trig_classes with the pass's mode
+ * (GPE_TRIG_RANGES, read once by gpe_create): 1, what those two do — the
+ * base classes general,
+ * mid, small; 2, the library's default — also 3 midlo (a cos node with
+ * |x| < 1.44 proven: COS_MIDLO, the table's entry after COS_SMALL) and 4 wide
+ * (every lane finite and |x| < 1e8: SIN_WIDE, COS_WIDE, the last two
+ * entries), and a sin/cos over a possibly non-finite value is bounded by
+ * [-1, 1] "or NaN", which mid, small and midlo accept (csrc/trig_ranges.h).
+ * Any other mode: an error. */
+int gpe_debug_translate_mode(const uint32_t* code, int64_t n_words,
+                                const int64_t* off, int64_t n_prog,
+                                const int32_t* depth, int nv, const uint32_t* table,
+                                int n_table, uint32_t* out, int64_t out_cap,
+                                int64_t* starts, int64_t* n_out, const double* lo,
+                                const double* hi, int mode);
+int gpe_debug_trig_classes_mode(const uint32_t* code, int64_t n_words, const double* lo,
+                            const double* hi, int nv, int mode, int32_t* out, int64_t cap);
+
+/* The sin/cos words of the last exact-core translation by the class whose
+ * handler was picked: out[0] general, out[1] mid, out[2] small, out[3] midlo,
+ * out[4] wide; their sum is that of gpe_last_trig_classes, which keeps
+ * counting the base classes (GPE_TRIG_RANGES=1's choice) in every mode.
+ * GPE_TRIG_RANGES=1: out[3] = out[4] = 0 and the rest is
+ * gpe_last_trig_classes'. */
+int gpe_last_trig_picked(const gpe_ctx* ctx, int64_t* out);
 
 /* Diagnostic: evaluate the device's sin (fn 0), cos (fn 1), square (fn 2),
  * the platform libm's sin (3) / cos (4), or sin (5) / cos (6) through the

@@ -9,10 +9,11 @@ gpe_debug_trig_classes) classifies every sin/cos node from the columns'
 bounds [-1, 1]; the words are evaluated on the first ``tiles`` 128-case tiles
 of the headline cases, and every sin/cos call's 128 arguments (chain k =
 cases 64k .. 64k + 63) run through the general handler and through the
-handler of the node's class.  Prints, per handler, the executed VALU (of
-them fp64), SALU and LDS instructions per wave-call, the class shares, and
-the weighted per-call totals of the specialised mix against the general
-handler alone.  Every result is checked bit for bit against the host libm,
+handler of the node's class, once with the base classes (GPE_TRIG_RANGES=1)
+and once with all of them (2, the default).  Prints, per mode and handler, the
+executed VALU (of them fp64), SALU and LDS instructions per wave-call, the
+class shares, and the weighted per-call totals of the specialised mix against
+the general handler alone, then the two modes side by side.  Every result is checked bit for bit against the host libm,
 and every argument against its class's range.
 
 Usage: python scripts/trig_range_counts.py [trees=192] [tiles=2]
@@ -31,8 +32,15 @@ import asm_emu                                   # noqa: E402
 from deap_amd import _lib, configs              # noqa: E402
 from deap_amd.flatten import Flattener, Op       # noqa: E402
 
-CLASS = ("general", "mid", "small")
-LIMIT = (math.inf, 2.42, 0.855)
+CLASS = ("general", "mid", "small", "midlo", "wide")
+LIMIT = (math.inf, 2.42, 0.855, 1.44, 1e8)
+
+
+def handler(kind, c):
+    """The handler of a node's class (midlo is a cos class: a sin node never
+    gets it)."""
+    assert not (kind == "sin" and c == 3)
+    return kind.upper() if c == 0 else "%s_%s" % (kind.upper(), CLASS[c].upper())
 
 
 def f64(lo, hi):
@@ -82,49 +90,47 @@ def trig_calls(words, X):
                 raise ValueError(op)
 
 
-def main():
-    n_trees = int(sys.argv[1]) if len(sys.argv) > 1 else 192
-    tiles = int(sys.argv[2]) if len(sys.argv) > 2 else 2
-    pset = configs.pset_for("symreg10")
-    pop = configs.population(pset, "half", n_trees, 2024, 4, 8)
-    batch = Flattener(pset).flatten(pop)
-    code = np.asarray(batch.code, dtype=np.uint32)
-    off = np.asarray(batch.offsets, dtype=np.int64)
-    X = np.ascontiguousarray(np.random.default_rng(2024).uniform(
-        -1.0, 1.0, size=(tiles * 128, 10)).T)
-    lo, hi = -np.ones(10), np.ones(10)
-    names = {(k, c): (k.upper() if c == 0 else "%s_%s" % (k.upper(), CLASS[c].upper()))
-             for k in ("sin", "cos") for c in range(3)}
-    lines = {h: asm_emu.handler_lines(h) for h in names.values()}
-    spec = {h: {} for h in names.values()}       # the node's class handler
-    gen = {h: {} for h in names.values()}        # the general one, same calls
-    calls = {h: 0 for h in names.values()}
-    bad = 0
+def count_mode(mode, n_trees, tiles, code, off, pop, calls_of, lo, hi, lines):
+    """One GPE_TRIG_RANGES mode on the same calls: prints its table, returns
+    (results that are not the host libm's, weighted totals per call)."""
+    names = sorted({handler(k, c) for k in ("sin", "cos") for c in range(5)
+                    if not (k == "sin" and c == 3)})
+    spec = {h: {} for h in names}                # the node's class handler
+    gen = {h: {} for h in names}                 # the general one, same calls
+    calls = {h: 0 for h in names}
+    bad = nan_calls = 0
     for i in range(n_trees):
         w = code[off[i]:off[i + 1]]
-        cls = _lib.debug_trig_classes(w, lo, hi)
-        got = trig_calls(w, X)
+        cls = _lib.debug_trig_classes(w, lo, hi, mode=mode)
+        got = calls_of[i]
         assert len(cls) == len(got)
         for c, (kind, arg) in zip(cls.tolist(), got):
-            h = names[(kind, c)]
+            h = handler(kind, c)
             f = math.sin if kind == "sin" else math.cos
             for t in range(tiles):
                 x = np.ascontiguousarray(arg[t * 128:(t + 1) * 128])
-                if not np.isfinite(x).all():
-                    assert c == 0
-                    continue
-                assert np.abs(x).max() < LIMIT[c], (str(pop[i]), CLASS[c])
-                ref = np.array([f(v) for v in x.tolist()]).view(np.uint64)
+                fin = np.isfinite(x)
+                if not fin.all():
+                    # general, or (mode 2) a NaN lane of a "bounded or NaN"
+                    # value in mid / small / midlo: never an inf, never wide
+                    assert c == 0 or (mode == 2 and c in (1, 2, 3) and not np.isinf(x).any())
+                    if c == 0:
+                        continue
+                    nan_calls += 1
+                assert np.abs(x[fin]).max(initial=0.0) < LIMIT[c], (str(pop[i]), CLASS[c])
+                ref = np.array([f(v) if math.isfinite(v) else math.nan
+                                for v in x.tolist()]).view(np.uint64)
                 y, _ = asm_emu.run_handler(h, x, lines=lines[h], counts=spec[h])
-                bad += int((y.view(np.uint64) != ref).sum())
-                g = names[(kind, 0)]
+                bad += int((y.view(np.uint64)[fin] != ref[fin]).sum() + (~np.isnan(y[~fin])).sum())
+                g = handler(kind, 0)
                 if c:
                     y, _ = asm_emu.run_handler(g, x, lines=lines[g], counts=gen[h])
-                    bad += int((y.view(np.uint64) != ref).sum())
+                    bad += int((y.view(np.uint64)[fin] != ref[fin]).sum())
                 calls[h] += 1
     total = sum(calls.values())
-    print("%d trees, %d tiles: %d sin/cos wave-calls; results not the host "
-          "libm's: %d" % (n_trees, tiles, total, bad))
+    print("GPE_TRIG_RANGES=%d: %d trees, %d tiles: %d sin/cos wave-calls (%d with NaN lanes "
+          "in a specialised handler); results not the host libm's: %d"
+          % (mode, n_trees, tiles, total, nan_calls, bad))
     print("| handler | share of calls | VALU | of them fp64 | SALU | LDS | "
           "general handler on the same calls: VALU / fp64 / SALU |")
     print("|---|---|---|---|---|---|---|")
@@ -153,6 +159,34 @@ def main():
           % (tot_g["valu"] / total, tot_s["valu"] / total,
              100.0 * (1 - tot_s["valu"] / tot_g["valu"]),
              tot_g["salu"] / total, tot_s["salu"] / total))
+    return bad, {k: v / total for k, v in tot_s.items()}
+
+
+def main():
+    n_trees = int(sys.argv[1]) if len(sys.argv) > 1 else 192
+    tiles = int(sys.argv[2]) if len(sys.argv) > 2 else 2
+    pset = configs.pset_for("symreg10")
+    pop = configs.population(pset, "half", n_trees, 2024, 4, 8)
+    batch = Flattener(pset).flatten(pop)
+    code = np.asarray(batch.code, dtype=np.uint32)
+    off = np.asarray(batch.offsets, dtype=np.int64)
+    X = np.ascontiguousarray(np.random.default_rng(2024).uniform(
+        -1.0, 1.0, size=(tiles * 128, 10)).T)
+    lo, hi = -np.ones(10), np.ones(10)
+    calls_of = [trig_calls(code[off[i]:off[i + 1]], X) for i in range(n_trees)]
+    lines = {handler(k, c): asm_emu.handler_lines(handler(k, c))
+             for k in ("sin", "cos") for c in range(5) if not (k == "sin" and c == 3)}
+    bad = 0
+    per_call = {}
+    for mode in (1, 2):
+        b, per_call[mode] = count_mode(mode, n_trees, tiles, code, off, pop, calls_of,
+                                       lo, hi, lines)
+        bad += b
+        print()
+    print("per average call, GPE_TRIG_RANGES=1 -> 2: VALU %.2f -> %.2f, fp64 %.2f -> %.2f, "
+          "SALU %.2f -> %.2f"
+          % (per_call[1]["valu"], per_call[2]["valu"], per_call[1]["valu_f64"],
+             per_call[2]["valu_f64"], per_call[1]["salu"], per_call[2]["salu"]))
     return 1 if bad else 0
 
 
