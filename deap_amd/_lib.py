@@ -790,9 +790,9 @@ class Context(object):
         ``which`` is an index or one of ``LAUNCHES``."""
         if isinstance(which, str):
             which = self.LAUNCHES.index(which)
-        g = (ctypes.c_int64 * 12)()
-        self._check(self.lib.gpe_last_launch_shape(self.h, int(which), g, 12),
+        g = (ctypes.c_int64 * 13)()
+        self._check(self.lib.gpe_last_launch_shape(self.h, int(which), g, 13),
                     "gpe_last_launch_shape")
         return dict(zip(("programs", "P", "wpb", "waves", "n_slots", "K",
                          "sdepth", "n_tiles", "tiles_per_group", "groups",
-                         "dbuf", "lds_bytes"), list(g)))
+                         "dbuf", "lds_bytes", "tile_loop"), list(g)))

@@ -21,6 +21,7 @@ struct Launch {
   int64_t programs = 0;
   int K = 0;                        // asm launches: the core's cases per lane
   bool dbuf = false;                // asm launches: two tile buffers (asm_dbuf)
+  bool resident = false;            // launched with the exact core's resident tile loop
   size_t lds = 0;                   // dynamic LDS bytes its launch passed (0: not launched)
   char* h_pin = nullptr;            // pinned staging of the slot upload
   size_t h_pin_cap = 0;
@@ -324,6 +325,8 @@ struct gpe_ctx {
   int asm_waves = 8;           // waves per f_eval_asm block (share a tile)
   int asm_lds_kb = 80;         // LDS per f_eval_asm block (2 blocks per CU)
   int asm_dbuf = 1;            // two tile buffers, LDS-DMA (GPE_ASM_DBUF)
+  int tile_loop = 1;           // the exact D = 5 core resident over a group's lean
+                               // tiles (GPE_TILE_LOOP=0: one core entry per tile)
   int lw_interleave = 1;       // interleaved lowering scratch (GPE_LOWER_IL)
   int neg_fold = 1;            // lowering's NEG peephole (GPE_NEG_PEEPHOLE=0: off)
   int exact_all = 1;           // GPE_EXACT_ALL: the exact cores (0: table cores + redo)

@@ -156,7 +156,7 @@ if GLIBC4:
 
 class Gen(object):
     def __init__(self, K, D, NV, TB0=32, SB=None, exact=False, trig_group=0,
-                 loop=False, typed=False):
+                 loop=False, typed=False, tile_loop=False):
         if SB is None:                      # the exact core: 16 more SGPRs
             SB = 40 if exact else 56
         self.K, self.D, self.NV = K, D, NV
@@ -169,6 +169,12 @@ class Gen(object):
         # is not lean): the caller's state live across the core is then a
         # few registers instead of its whole program loop
         self.loop = loop
+        # tile_loop (the exact D = 5 core): the core also runs the wave over
+        # the lean tiles that follow (Gen.tile_next): between two tiles it
+        # meets the block's other waves, changes the tile buffer and issues
+        # the next tile's LDS-DMA itself; nothing of its prologue runs again
+        assert not tile_loop or (loop and exact)
+        self.tile_loop = tile_loop
         # typed: no sin/cos (no trig constants or table); the STGP families,
         # NOT and if_then_else; the loop's END counts hits (bool(T) is
         # bool(label)) instead of summing squared errors
@@ -2358,7 +2364,7 @@ class Gen(object):
         self.e("s_nop 4")              # the caller's writes of the inputs
         self.label(".Lnext_")
         self.e("s_cmp_ge_u32 s%d, %%[nmine]" % self.SJ)
-        self.e("s_cbranch_scc1 .Lend_%=")
+        self.e("s_cbranch_scc1 %s" % (".Ltile_%=" if self.tile_loop else ".Lend_%="))
         self.e("s_bitcmp1_b32 %%[done], s%d" % self.SJ)
         self.e("s_cbranch_scc1 .Lskip_%=")
         if self.prefetch:
@@ -2383,6 +2389,71 @@ class Gen(object):
             # the next load into the same SGPRs (or the core's exit)
             self.e("s_waitcnt lgkmcnt(0)")
         self.e("s_add_u32 s%d, s%d, 1" % (self.SJ, self.SJ))
+        self.e("s_branch .Lnext_%=")
+        if self.tile_loop:
+            self.tile_next()
+
+    def tile_next(self):
+        """.Ltile: the wave has run its last program of tile %[tio].  While
+        the next tile is inside the resident stretch (%[tio] + 1 < %[tend]:
+        full lean tiles, each copied into the other tile buffer by LDS-DMA
+        while its predecessor runs) the core goes on to it as f_eval_asm's
+        tile loop does: wait for this wave's copies of that tile, meet the
+        block's other waves (their copies have landed, and nobody reads the
+        tile just run any more), change buffers (%[xa], %[vts] move by
+        %[bflip], which changes sign), issue this wave's share of the tile
+        after it into the buffer just left, and start over at program 0.
+        Else it leaves with %[jio] = %[nmine].  A wave with no program, or a
+        wave re-entered after the caller finished its last program, comes
+        here at once from .Lnext: every wave of the block passes the one
+        s_barrier once per tile change (check_tile_loop).
+
+        This wave's columns: lane i of (%[dlo], %[dhi]) holds the address of
+        its i-th column's case 0 (0: no more), lane i of %[ddst] the column's
+        LDS byte address in tile buffer 0.  A column of a tile is 1 KiB
+        (K = 2 x 64 doubles, global_load_lds_dwordx4: 16 bytes per lane)."""
+        assert self.K == 2
+        W, NX = self.WIN, self.NXT       # (the window SGPRs are dead here)
+        VL = self.POOL0                  # lane * 16
+        self.label(".Ltile_")
+        self.e("s_add_u32 s%d, %%[tio], 1" % NX)
+        self.e("s_cmp_lt_u32 s%d, %%[tend]" % NX)
+        self.e("s_cbranch_scc0 .Lend_%=")
+        self.e("s_waitcnt vmcnt(0)")
+        self.e("s_barrier")
+        self.e("s_mov_b32 %%[tio], s%d" % NX)
+        self.e("v_add_u32_e32 %[xa], %[bflip], %[xa]")
+        self.e("v_add_u32_e32 %[vts], %[bflip], %[vts]")
+        self.e("s_sub_u32 %[bflip], 0, %[bflip]")
+        self.e("s_add_u32 s%d, s%d, 1" % (NX, NX))
+        self.e("s_cmp_lt_u32 s%d, %%[tend]" % NX)
+        self.e("s_cbranch_scc0 .Ltile_run_%=")
+        # tile %[tio] + 1 (s<NX>): its byte offset in a column (64 bits),
+        # the buffer it goes to (the one just left: buffer 1 iff the next
+        # change moves up) and lane * 16
+        self.e("s_lshl_b32 s%d, s%d, 10" % (W + 2, NX))
+        self.e("s_lshr_b32 s%d, s%d, 22" % (W + 3, NX))
+        self.e("s_max_i32 s%d, %%[bflip], 0" % (W + 4))
+        self.e("s_mov_b32 s%d, 0" % (W + 5))
+        self.e("v_mbcnt_lo_u32_b32 v%d, -1, 0" % VL)
+        self.e("v_mbcnt_hi_u32_b32 v%d, -1, v%d" % (VL, VL))
+        self.e("v_lshlrev_b32_e32 v%d, 4, v%d" % (VL, VL))
+        self.label(".Ltile_dma_")
+        self.e("v_readlane_b32 s%d, %%[dlo], s%d" % (W, W + 5))
+        self.e("v_readlane_b32 s%d, %%[dhi], s%d" % (W + 1, W + 5))
+        self.e("v_readlane_b32 s%d, %%[ddst], s%d" % (W + 6, W + 5))
+        self.e("s_nop 4")
+        self.e("s_cmp_eq_u64 %s, 0" % self.sp(W))
+        self.e("s_cbranch_scc1 .Ltile_run_%=")
+        self.e("s_add_u32 s%d, s%d, s%d" % (W, W, W + 2))
+        self.e("s_addc_u32 s%d, s%d, s%d" % (W + 1, W + 1, W + 3))
+        self.e("s_add_u32 m0, s%d, s%d" % (W + 6, W + 4))
+        self.e("s_nop 0")
+        self.e("global_load_lds_dwordx4 v%d, %s" % (VL, self.sp(W)))
+        self.e("s_add_u32 s%d, s%d, 1" % (W + 5, W + 5))
+        self.e("s_branch .Ltile_dma_%=")
+        self.label(".Ltile_run_")
+        self.e("s_mov_b32 s%d, 0" % self.SJ)
         self.e("s_branch .Lnext_%=")
 
     def load_first_window(self, sj):
@@ -2871,6 +2942,70 @@ def check_exec(lines, saved):
                 i += 1
 
 
+def check_tile_loop(lines, saved, sj):
+    """The resident tile loop's barrier (Gen.tile_next): the 8 waves of a
+    block must reach it the same number of times, once per tile change.  On
+    the emitted lines: there is one s_barrier; .Ltile is entered only from
+    .Lnext's end-of-programs test (so a wave without programs, and one
+    re-entered after its last program, take it like any other); every path
+    from .Ltile either leaves the core (.Lend) without a barrier, or passes
+    the barrier exactly once with EXEC never changed from `saved`, resets the
+    program index s<sj> and the only way back is .Lnext; and nothing else
+    sets s<sj> back.  Raises AssertionError otherwise."""
+    lab = {l[:-1]: i for i, l in enumerate(lines)
+           if l.endswith(":") and not l.startswith(("s_", "v_"))}
+    assert sum(l.split()[0] == "s_barrier" for l in lines) == 1, "one s_barrier"
+    to_tile = [i for i, l in enumerate(lines) if l.endswith(" .Ltile_%=")]
+    assert len(to_tile) == 1 and lines[to_tile[0]].startswith("s_cbranch_scc1") \
+        and lines[to_tile[0] - 1].startswith("s_cmp_ge_u32 s%d, %%[nmine]" % sj) \
+        and lines[to_tile[0] - 2] == ".Lnext_%=:", ".Ltile is .Lnext's end of programs"
+    # no fall-through into .Ltile
+    assert lines[lab[".Ltile_%="] - 1].startswith("s_branch"), "fall into .Ltile"
+    reset = "s_mov_b32 s%d, 0" % sj
+    resets = [i for i, l in enumerate(lines) if l == reset]
+    seen, ends = set(), set()
+    stack = [(lab[".Ltile_%="], 0, False)]
+    while stack:
+        i, nbar, zero = stack.pop()
+        while True:
+            assert i < len(lines), "ran off the core"
+            if (i, nbar, zero) in seen:
+                break
+            seen.add((i, nbar, zero))
+            l = lines[i]
+            if l == ".Lend_%=:":
+                assert nbar == 0 and not zero, "left the core after the barrier"
+                ends.add("end")
+                break
+            if l == ".Lnext_%=:":
+                assert nbar == 1 and zero, "tile change without its barrier / reset"
+                ends.add("next")
+                break
+            assert not l.startswith(".Lh_"), "fell into a handler"
+            assert not re.match(r"(s_\w+ exec,|v_cmpx|s_setpc)", l), \
+                "EXEC changed or a jump in the tile change: %r" % l
+            if l.split()[0] == "s_barrier":
+                nbar += 1
+            if l == reset:
+                assert nbar == 1
+                zero = True
+            m = re.match(r"s_(cbranch_\w+|branch) (\S+)$", l)
+            if m:
+                assert m.group(2) in lab, m.group(2)
+                if m.group(1) == "branch":
+                    i = lab[m.group(2)]
+                    continue
+                stack.append((lab[m.group(2)], nbar, zero))
+            i += 1
+    assert ends == {"end", "next"}, ends
+    tile = range(lab[".Ltile_%="], lab[".Ltile_run_%="] + 3)
+    assert all(i in tile for i in resets) and len(resets) == 1, "s%d reset elsewhere" % sj
+    # EXEC at .Ltile is the handlers' (check_exec: every handler restores it
+    # before its jump; .Lnext and END do not write it)
+    a, b = lab[".Lnext_%="], lab[".Ltile_%="]
+    assert not any(re.match(r"(s_\w+ exec,|v_cmpx)", l) for l in lines[a:b]), "EXEC in .Lnext"
+
+
 def trig_data():
     """Table + constants of the table-driven sin/cos (trig_table.json)."""
     import json
@@ -2916,8 +3051,12 @@ def emit(K, D, NV, suffix="", out_dir=HERE, trig_group=0):
     tb0 = int(os.environ.get("GEN_ASM_TB0", "32")) if suffix == "" else 32
     # trig_group: sin/cos chains interleaved that many at a time (0: all K);
     # K = 4 cores run them one by one (their temporaries set the VGPRs)
+    # the exact D = 5 core (the product's) also runs the tile loop of a lean
+    # stretch (Gen.tile_next; GEN_ASM_TILE_LOOP=0, a variant build: without)
+    tile_loop = suffix == "_exact" and loop and \
+        os.environ.get("GEN_ASM_TILE_LOOP", "1") == "1"
     g = Gen(K, D, NV, TB0=tb0, exact=exact, loop=loop, typed=typed,
-            trig_group=trig_group).build()
+            trig_group=trig_group, tile_loop=tile_loop).build()
     # experiment knob: reserve more VGPRs (clobbered, unused) to price the
     # occupancy a register-hungrier core would have
     g.vmax += int(os.environ.get("GEN_ASM_PAD_VGPRS", "0")) if not suffix else 0
@@ -2926,6 +3065,8 @@ def emit(K, D, NV, suffix="", out_dir=HERE, trig_group=0):
     body = g.lines
     if exact:
         check_exec(body, g.sp(g.SMASK))
+    if g.tile_loop:
+        check_tile_loop(body, g.sp(g.SMASK), g.SJ)
     inc = os.path.join(out_dir, "gp_asm_core%s.inc" % suffix)
     with open(inc, "w") as fh:
         fh.write("// GENERATED by gen_asm.py (K=%d, D=%d, NV=%d) — do not edit\n"
@@ -2933,6 +3074,8 @@ def emit(K, D, NV, suffix="", out_dir=HERE, trig_group=0):
         if suffix in ("", "_exact"):
             fh.write("#define GP_ASM_LOOP%s %d\n" % (suffix.upper(),
                                                      1 if g.loop else 0))
+        if suffix == "_exact":
+            fh.write("#define GP_ASM_TILE_LOOP_EXACT %d\n" % (1 if g.tile_loop else 0))
         fh.write("#define GP_ASM_CORE%s \\\n" % S)
         for l in body:
             fh.write('  "%s\\n" \\\n' % l)

@@ -1659,6 +1659,7 @@ int gpe_create(int device, gpe_ctx** out) {
   if ((env = getenv("GPE_ASM_LDS_KB")) && atoi(env) >= 16 && atoi(env) <= 160)
     ctx->asm_lds_kb = atoi(env);
   if ((env = getenv("GPE_ASM_DBUF"))) ctx->asm_dbuf = atoi(env) != 0;
+  if ((env = getenv("GPE_TILE_LOOP"))) ctx->tile_loop = atoi(env) != 0;
   if ((env = getenv("GPE_LOWER_IL"))) ctx->lw_interleave = atoi(env) != 0;
   if ((env = getenv("GPE_NEG_PEEPHOLE"))) ctx->neg_fold = atoi(env) != 0;
   if ((env = getenv("GPE_ASM_DEEP_WAVES")) && (atoi(env) == 4 || atoi(env) == 8))
@@ -3525,7 +3526,8 @@ int gpe_last_launch_shape(const gpe_ctx* ctx, int which, int64_t* o, int n) {
   }
   const int64_t g[GPE_LAUNCH_SHAPE_FIELDS] = {
       L->programs, L->P, L->wpb, L->waves, L->n_slots, L->K, L->sdepth, L->n_tiles,
-      L->tiles_per_group, L->groups, L->dbuf ? 1 : 0, (int64_t)L->lds};
+      L->tiles_per_group, L->groups, L->dbuf ? 1 : 0, (int64_t)L->lds,
+      L->resident ? 1 : 0};
   std::copy(g, g + std::min(n, GPE_LAUNCH_SHAPE_FIELDS), o);
   return 0;
 }

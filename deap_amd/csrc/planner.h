@@ -380,6 +380,12 @@ int launch_asm(gpe_ctx* ctx, Launch& L, unsigned long long* err,
     a.cst = ctx->d_cst_exact;
   }
   a.dbuf = L.dbuf ? 1 : 0;
+  // the resident tile loop: f_eval_asm's conditions (its kResident core on a
+  // lean, double-buffered launch)
+  L.resident = exact && !deep_core && GP_ASM_LOOP_EXACT && GP_ASM_TILE_LOOP_EXACT &&
+               ctx->tile_loop && L.dbuf && L.K * 64 * sizeof(double) == 1024 &&
+               a.nt == 1 && a.case_out == nullptr && a.n_tiles < (1ll << 31);
+  a.tile_loop = L.resident ? 1 : 0;
   const size_t lds = lds_bytes_asm(ctx, L.P, L.wpb, L.K, L.dbuf, exact);
   L.lds = lds;
   const bool f32 = ctx->prec == GPE_PREC_F32;

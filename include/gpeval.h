@@ -381,8 +381,11 @@ int gpe_last_geometry_ex(const gpe_ctx* ctx, int64_t* out, int n);
  * programs, programs per wave, waves per block, waves, slots (waves x
  * programs per wave, -1 padded), cases per lane of an asm core (0: a C++
  * kernel), stack slots, case tiles, tiles per group, tile groups, two tile
- * buffers (0 / 1), and the dynamic LDS bytes the launch passed to its kernel
- * (0: planned but not launched, or no programs).  Writes the first
+ * buffers (0 / 1), the dynamic LDS bytes the launch passed to its kernel
+ * (0: planned but not launched, or no programs), and whether the launch ran
+ * with the exact core's resident tile loop (0 / 1: the exact D = 5 core on a
+ * lean launch — one target column, no per-case output — with two tile
+ * buffers, unless GPE_TILE_LOOP=0, read once by gpe_create).  Writes the first
  * min(n, GPE_LAUNCH_SHAPE_FIELDS) fields; GPE_E_INVALID for another `which`. */
 #define GPE_LAUNCH_ASM_FAST 0
 #define GPE_LAUNCH_ASM_DEEP 1
@@ -391,7 +394,7 @@ int gpe_last_geometry_ex(const gpe_ctx* ctx, int64_t* out, int n);
 #define GPE_LAUNCH_CPP_DEEP 4
 #define GPE_LAUNCH_FASM 5
 #define GPE_LAUNCH_DASM 6
-#define GPE_LAUNCH_SHAPE_FIELDS 12
+#define GPE_LAUNCH_SHAPE_FIELDS 13
 int gpe_last_launch_shape(const gpe_ctx* ctx, int which, int64_t* out, int n);
 
 /* Diagnostic (host only): the program -> threaded-code translation the asm
