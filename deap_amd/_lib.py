@@ -749,6 +749,9 @@ class Context(object):
         return {"comm_ms": ms[0], "redo_ms": ms[1]}
 
     def math_probe(self, fn, x):
+        """gpe_math_probe (include/gpeval.h lists the function numbers; 15 /
+        16: the C++ kernels' fp64 / fp32 square root; 17 / 18: the exact and the
+        fp32 asm cores' SQRT handlers)."""
         x = np.ascontiguousarray(x, dtype=np.float64)
         y = np.zeros_like(x)
         self._check(self.lib.gpe_math_probe(self.h, int(fn), _ptr(x), _ptr(y),

@@ -53,6 +53,12 @@ def if_then_else(condition, out1, out2):
     return out1 if condition else out2
 
 
+def psqrt(x):
+    """The protected square root of symbolic regression: never raises for
+    a float."""
+    return math.sqrt(abs(x))
+
+
 def rand101():
     """examples/gp/symbreg.py:43."""
     return random.randint(-1, 1)
@@ -63,8 +69,9 @@ def rand100():
     return random.random() * 100
 
 
-def arith_pset(n_args, rename_x=False, trig=True):
-    """symbreg.py:35-44 primitive set (with *n_args* arguments)."""
+def arith_pset(n_args, rename_x=False, trig=True, extra=()):
+    """symbreg.py:35-44 primitive set (with *n_args* arguments); *extra*:
+    further unary primitives."""
     pset = gp.PrimitiveSet("MAIN", n_args)
     pset.addPrimitive(operator.add, 2)
     pset.addPrimitive(operator.sub, 2)
@@ -74,6 +81,8 @@ def arith_pset(n_args, rename_x=False, trig=True):
     if trig:
         pset.addPrimitive(math.cos, 1)
         pset.addPrimitive(math.sin, 1)
+    for fn in extra:
+        pset.addPrimitive(fn, 1)
     pset.addEphemeralConstant("rand101", rand101)
     if rename_x:
         pset.renameArguments(ARG0="x")
@@ -180,6 +189,12 @@ def pset_for(name):
             "symbreg": lambda: arith_pset(1, rename_x=True),
             "symreg10": lambda: arith_pset(10),
             "symreg10_notrig": lambda: arith_pset(10, trig=False),
+            # what a symbolic-regression user adds first: abs and a
+            # protected square root; _sqrt: math.sqrt too (ValueError for a
+            # negative argument)
+            "symreg10_abs": lambda: arith_pset(10, extra=(abs, psqrt)),
+            "symreg10_sqrt": lambda: arith_pset(
+                10, extra=(abs, psqrt, math.sqrt)),
             "mux11": mux_pset,
             "parity6": parity_pset,
             "spambase": spam_pset,
@@ -202,7 +217,7 @@ def spec_for(name, data=None):
     kind = data.get("kind")
     if name == "symbreg":
         return SymbRegMSE.quartic()
-    if name == "symreg10":
+    if name in ("symreg10", "symreg10_abs", "symreg10_sqrt"):
         X, y = datasets.symreg10_cases(data.get("n", 2 ** 20),
                                        data.get("seed", 2024))
         return SymbRegMSE(X, y)

@@ -377,6 +377,23 @@ HD bool run(const uint32_t* W, const uint32_t* ints, XV xv, Num& T, uint32_t& er
       T = from_f(glibc_trig(v, op == OP_COS));
       continue;
     }
+    if (op == OP_ABS) {                  // abs(int) is an int; index field 1:
+      if (x) {                           // math.fabs, float(int) first
+        const double v = to_f(T, err);
+        if (err) return true;
+        T = from_f(__builtin_fabs(v));
+      } else {
+        T = T.isint ? from_int(false, T.m) : from_f(__builtin_fabs(T.f));
+      }
+      continue;
+    }
+    if (op == OP_SQRT) {                 // math.sqrt: float(int) first
+      const double v = to_f(T, err);
+      if (err) return true;
+      if (v < 0.0) err = E_VALUE;
+      T = from_f(__builtin_sqrt(v));
+      continue;
+    }
     if (op == OP_NOT) { T = from_bool(!truth(T)); continue; }
     if (op == OP_ITE) { T = truth(stk[d]) ? stk[d + 1] : T; continue; }
     if (op < OP_ADD || op >= OP_XOR) return false;
@@ -457,6 +474,23 @@ bool run(const uint32_t* W, const Rows& ints, XV xv, Num& T, uint32_t& err) {
       if (err) return true;
       if (__builtin_isinf(v)) err = E_VALUE;
       T = from_f(glibc_trig(v, op == OP_COS));
+      continue;
+    }
+    if (op == OP_ABS) {                  // abs(int) is an int; index field 1:
+      if (x) {                           // math.fabs, float(int) first
+        const double v = to_f(T, err);
+        if (err) return true;
+        T = from_f(__builtin_fabs(v));
+      } else {
+        T = T.isint ? from_int(false, T.m) : from_f(__builtin_fabs(T.f));
+      }
+      continue;
+    }
+    if (op == OP_SQRT) {                 // math.sqrt: float(int) first
+      const double v = to_f(T, err);
+      if (err) return true;
+      if (v < 0.0) err = E_VALUE;
+      T = from_f(__builtin_sqrt(v));
       continue;
     }
     if (op == OP_NOT) { T = from_bool(!truth(T)); continue; }

@@ -177,6 +177,24 @@ __device__ __forceinline__ void f_run(const ProgWords& W, const R* xs,
           FOR_K T[k] = trig_x<EXACT>(T[k], op == OP_COS, gtab);
         }
         break;
+      case OP_ABS:                       // the sign bit cleared (nan stays nan)
+        if constexpr (std::is_same<R, double>::value) {
+          FOR_K T[k] = __builtin_fabs(T[k]);
+        } else {
+          FOR_K T[k] = __builtin_fabsf(T[k]);
+        }
+        break;
+      case OP_SQRT:
+        // math.sqrt: ValueError for a negative argument (-inf included; -0.0
+        // and nan are not < 0); IEEE sqrt, correctly rounded (the compiler's
+        // refined sequence, not the bare v_sqrt), nan for a negative lane
+        FOR_K vbits |= (uint32_t)(T[k] < zero) << k;
+        if constexpr (std::is_same<R, double>::value) {
+          FOR_K T[k] = __builtin_sqrt(T[k]);
+        } else {
+          FOR_K T[k] = __builtin_sqrtf(T[k]);
+        }
+        break;
       case OP_NOT:
         FOR_K T[k] = (T[k] == zero) ? one : zero;
         break;
@@ -561,8 +579,12 @@ __global__ void math_probe(int fn, const double* x, double* y, int64_t n) {
   const double v = x[i];
   double sn, cs;
   gp_sincos(v, sn, cs);
+  // 15 / 16: f_run's SQRT case, fp64 / fp32 (the compiler's correctly
+  // rounded sequences; a negative argument gives nan)
   y[i] = fn == 0 ? sn : fn == 1 ? cs : fn == 2 ? v * v : fn == 3 ? sin(v)
-       : fn == 4 ? cos(v) : fn >= 11 ? glibc_trig(v, fn == 12)
+       : fn == 4 ? cos(v) : fn == 15 ? __builtin_sqrt(v)
+       : fn == 16 ? (double)__builtin_sqrtf((float)v)
+       : fn >= 11 ? glibc_trig(v, fn == 12)
        : (double)gp_trig32((float)v, fn == 10);
 }
 

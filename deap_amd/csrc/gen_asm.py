@@ -590,6 +590,103 @@ class Gen(object):
         else:
             raise KeyError(fam)
 
+    # -------------------------------------------------------- abs, sqrt --
+    def defer_handler(self, name):
+        """A handler id at this place of the layout whose body comes later
+        (deferred_bodies, after every other handler): the handlers between
+        keep their addresses."""
+        self.handlers.append((name, ".Lh_%s_" % name))
+
+    def sqrt_all(self):
+        """T_k = sqrt(T_k), correctly rounded: the sequence the compiler emits
+        for __builtin_sqrt on gfx950, 17 VALU per value — x < 2^-767 scaled by
+        2^256 (v_ldexp_f64), y = v_rsq_f64(x), g = x y, h = y / 2, one
+        Goldschmidt step (r = 1/2 - h g; g += g r; h += h r), two residual
+        corrections (d = x - g g; g += d h), the scale undone (2^-128), and
+        +-0 / +inf passed through (v_cmp_class_f64); a nan goes through the
+        arithmetic, a negative x gives nan.  The cases' chains interleaved two
+        at a time, as the division bodies (the second chain's masks in BASE).
+        A negative lane must end in ValueError: its high word (>= 2^31
+        unsigned, past every redo threshold) goes into VRED's running
+        maximum, so the program's END leaves for the C++ finish exactly as
+        for an infinite sin/cos argument (no new exit, EXEC untouched); -0.0
+        leaves too and gets its -0.0 there."""
+        K, P = self.K, self.p
+        sets = [[self.POOL0 + i for i in range(10)],
+                [self.OB + 2 * K + i for i in range(10)]]
+        self.use_v(sets[1][9])
+        c100, cm80 = sets[0][8], sets[0][9]
+        CA, NXT = self.CA, self.NXT        # free: no inline constant here
+        M = ["vcc", self.sp(self.BASE)]
+        self.e("s_mov_b32 s%d, 0" % CA)
+        self.e("s_brev_b32 s%d, 8" % (CA + 1))          # 2^-767
+        self.e("s_movk_i32 s%d, 0x260" % NXT)           # -0, +0, +inf
+        self.e("v_mov_b32_e32 v%d, 0x100" % c100)
+        self.e("v_mov_b32_e32 v%d, 0xffffff80" % cm80)
+        neg = [sets[k % 2][7] if k < 2 else sets[k % 2][6] for k in range(K)]
+        assert K <= 4
+        for k in range(K):
+            self.e("v_and_b32_e32 v%d, 0x80000000, v%d" % (neg[k], self.T(k) + 1))
+        for k in range(0, K - 1, 2):
+            self.e("v_max3_u32 v%d, v%d, v%d, v%d"
+                   % (self.VRED, self.VRED, neg[k], neg[k + 1]))
+        if K % 2:
+            self.e("v_max_u32_e32 v%d, v%d, v%d" % (self.VRED, self.VRED, neg[K - 1]))
+        for k0 in range(0, K, 2):
+            ch = [(self.T(k), sets[j], M[j]) for j, k in enumerate(range(k0, min(K, k0 + 2)))]
+
+            def each(fmt):
+                for x, t, m in ch:
+                    self.e(fmt.format(x=P(x), xlo="v%d" % x, xhi="v%d" % (x + 1),
+                                      y=P(t[0]), g=P(t[2]), r=P(t[4]), e="v%d" % t[6],
+                                      glo="v%d" % t[2], ghi="v%d" % (t[3]), m=m,
+                                      lim=self.sp(CA), c100="v%d" % c100,
+                                      cm80="v%d" % cm80, cls="s%d" % NXT))
+            # (gfx950: two wait states between a VALU write of an SGPR pair
+            # and a VALU read of it, one after a transcendental: the
+            # compiler's own sequence carries the same s_nops)
+            each("v_cmp_gt_f64_e64 {m}, {lim}, {x}")
+            self.e("s_nop 1")
+            each("v_cndmask_b32_e64 {e}, 0, {c100}, {m}")
+            each("v_ldexp_f64 {x}, {x}, {e}")
+            each("v_cndmask_b32_e64 {e}, 0, {cm80}, {m}")
+            each("v_rsq_f64_e32 {y}, {x}")
+            self.e("s_nop 0")
+            each("v_mul_f64 {g}, {x}, {y}")
+            each("v_mul_f64 {y}, {y}, 0.5")
+            each("v_fma_f64 {r}, -{y}, {g}, 0.5")
+            each("v_fma_f64 {g}, {g}, {r}, {g}")
+            each("v_fma_f64 {y}, {y}, {r}, {y}")
+            for _ in range(2):
+                each("v_fma_f64 {r}, -{g}, {g}, {x}")
+                each("v_fma_f64 {g}, {r}, {y}, {g}")
+            each("v_ldexp_f64 {g}, {g}, {e}")
+            each("v_cmp_class_f64_e64 {m}, {x}, {cls}")
+            self.e("s_nop 1")
+            each("v_cndmask_b32_e64 {xlo}, {glo}, {xlo}, {m}")
+            each("v_cndmask_b32_e64 {xhi}, {ghi}, {xhi}, {m}")
+
+    def deferred_bodies(self):
+        """The bodies of ABS and SQRT (ids beside NEG: defer_handler)."""
+        for name in ("ABS", "SQRT"):
+            if self.align:
+                self.e(".p2align %d" % self.align)
+            self.label(".Lh_%s_" % name)
+            self.dispatch_head()
+            self.e("s_waitcnt lgkmcnt(0)")
+            if name == "ABS":              # the sign bit cleared, as abs(x)
+                for k in range(self.K):
+                    self.e("v_and_b32_e32 v%d, 0x7fffffff, v%d"
+                           % (self.T(k) + 1, self.T(k) + 1))
+            else:
+                tier = self.prio is not None and len(self.prio) > 2
+                if tier:
+                    self.e("s_setprio %d" % self.prio[2])
+                self.sqrt_all()
+                if tier:
+                    self.e("s_setprio %d" % self.prio[0])
+            self.dispatch_tail()
+
     def set_bool(self, k):
         """T_k = VCC ? 1.0 : 0.0 (the F machine's bools)."""
         tk = self.T(k)
@@ -2782,6 +2879,9 @@ class Gen(object):
             self.e("v_xor_b32_e32 v%d, 0x80000000, v%d"
                    % (self.T(k) + 1, self.T(k) + 1))
         self.dispatch_tail()
+        if not self.typed:                 # (ids here, bodies after the rest)
+            self.defer_handler("ABS")
+            self.defer_handler("SQRT")
         if self.typed:
             self.handler("NOT")
             self.dispatch_head()
@@ -2840,6 +2940,7 @@ class Gen(object):
             self.dispatch_tail()
         if not self.typed:
             self.range_handlers()
+            self.deferred_bodies()
         # ---- probe: write the handler offset table
         self.label(".Lprobe_")
         self.probe_stores(self.POOL0, self.POOL0 + 1)
@@ -2883,6 +2984,7 @@ class Gen(object):
                "H_PUSH0": base_push, "H_PUSHC0": base_pushc,
                "H_PUSHV0": base_pushv, "H_BIN0": base_bin,
                "H_FAM_STRIDE": stride, "H_NEG": ids["NEG"],
+               "H_ABS": ids.get("ABS", -1), "H_SQRT": ids.get("SQRT", -1),
                "H_SIN": ids.get("SIN", -1), "H_COS": ids.get("COS", -1),
                "H_SIN_MID": ids.get("SIN_MID", -1),
                "H_COS_MID": ids.get("COS_MID", -1),

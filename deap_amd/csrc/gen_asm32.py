@@ -192,6 +192,62 @@ class Gen32(gen_asm.Gen):
         else:
             raise KeyError(fam)
 
+    # -------------------------------------------------------- abs, sqrt --
+    def sqrt_all(self):
+        """T_k = sqrtf(T_k), correctly rounded: the compiler's gfx950 sequence
+        for __builtin_sqrtf — x < 2^-96 scaled by 2^32, v_sqrt_f32, the
+        neighbours s -+ 1 ulp tried by their residuals, the scale undone
+        (2^-16), +-0 / +inf passed through.  A negative lane (the reference's
+        ValueError) sets the case's VRED key to 0, below RED_INF: the
+        (program, tile) pair is re-run on the C++ kernels, which report it."""
+        t = [self.POOL0 + i for i in range(6)]
+        self.use_v(t[5])
+        S = self.sp(self.BASE)
+        self.e("s_movk_i32 s%d, 0x260" % self.NXT)          # -0, +0, +inf
+        for k in range(self.K):
+            x = self.T(k)
+            s_, lo, hi, rl, rh, u = t
+            self.e("v_ashrrev_i32_e32 v%d, 31, v%d" % (u, x))   # -1: sign set
+            self.e("v_not_b32_e32 v%d, v%d" % (u, u))
+            self.e("v_min_u32_e32 v%d, v%d, v%d" % (self.VRED + k, self.VRED + k, u))
+            self.e("v_mul_f32_e32 v%d, 0x4f800000, v%d" % (s_, x))
+            self.e("v_cmp_gt_f32_e32 vcc, 0xf800000, v%d" % x)
+            self.e("s_nop 1")
+            self.e("v_cndmask_b32_e32 v%d, v%d, v%d, vcc" % (x, x, s_))
+            self.e("v_sqrt_f32_e32 v%d, v%d" % (s_, x))
+            self.e("s_nop 0")
+            self.e("v_add_u32_e32 v%d, -1, v%d" % (lo, s_))
+            self.e("v_add_u32_e32 v%d, 1, v%d" % (hi, s_))
+            self.e("v_fma_f32 v%d, -v%d, v%d, v%d" % (rl, lo, s_, x))
+            self.e("v_fma_f32 v%d, -v%d, v%d, v%d" % (rh, hi, s_, x))
+            self.e("v_cmp_ge_f32_e64 %s, 0, v%d" % (S, rl))
+            self.e("s_nop 1")
+            self.e("v_cndmask_b32_e64 v%d, v%d, v%d, %s" % (s_, s_, lo, S))
+            self.e("v_cmp_lt_f32_e64 %s, 0, v%d" % (S, rh))
+            self.e("s_nop 1")
+            self.e("v_cndmask_b32_e64 v%d, v%d, v%d, %s" % (s_, s_, hi, S))
+            self.e("v_mul_f32_e32 v%d, 0x37800000, v%d" % (lo, s_))
+            self.e("v_cndmask_b32_e32 v%d, v%d, v%d, vcc" % (s_, s_, lo))
+            self.e("v_cmp_class_f32_e64 vcc, v%d, s%d" % (x, self.NXT))
+            self.e("s_nop 1")
+            self.e("v_cndmask_b32_e32 v%d, v%d, v%d, vcc" % (x, s_, x))
+
+    def deferred_bodies(self):
+        for name in ("ABS", "SQRT"):
+            self.label(".Lh_%s_" % name)
+            self.dispatch_head()
+            if name == "ABS":
+                for k in range(self.K):
+                    self.e("v_and_b32_e32 v%d, 0x7fffffff, v%d"
+                           % (self.T(k), self.T(k)))
+            else:
+                if self.prio:
+                    self.e("s_setprio %d" % self.prio[2])
+                self.sqrt_all()
+                if self.prio:
+                    self.e("s_setprio %d" % self.prio[0])
+            self.dispatch_tail()
+
     # ---------------------------------------------------------- sin/cos --
     def trig_ops32(self, k, want):
         """gp_trig32() for case k: (template, defs, uses); all singles."""
@@ -388,6 +444,8 @@ class Gen32(gen_asm.Gen):
             self.e("v_xor_b32_e32 v%d, 0x80000000, v%d"
                    % (self.T(k), self.T(k)))
         self.dispatch_tail()
+        self.defer_handler("ABS")      # (ids beside NEG, bodies at the end:
+        self.defer_handler("SQRT")     # one layout with gen_asm.py's cores)
         for want in ("sin", "cos"):
             self.handler(want.upper())
             self.dispatch_head(alias_entry=".Lalias_%s_" % want.upper())
@@ -398,6 +456,7 @@ class Gen32(gen_asm.Gen):
                 self.e("s_setprio %d" % self.prio[0])
             self.dispatch_tail()
         self.range_handlers()          # (aliases of SIN / COS: one layout)
+        self.deferred_bodies()
         self.label(".Lprobe_")
         self.probe_stores(self.POOL0, self.POOL0 + 1)
         self.label(".Lend_")

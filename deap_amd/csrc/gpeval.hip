@@ -81,7 +81,7 @@ enum : uint32_t {
   OP_ADD = 8, OP_SUB = 11, OP_RSUB = 14, OP_MUL = 17, OP_DIV = 20,
   OP_RDIV = 23, OP_LT = 26, OP_GT = 29, OP_EQ = 32, OP_AND = 35, OP_OR = 38,
   OP_XOR = 41, OP_NEG = 48, OP_SIN = 49, OP_COS = 50, OP_NOT = 51,
-  OP_ITE = 52, OP_NPDIV = 56, OP_RNPDIV = 59
+  OP_ITE = 52, OP_ABS = 53, OP_SQRT = 54, OP_NPDIV = 56, OP_RNPDIV = 59
 };
 
 constexpr int kWaves = 4;
@@ -251,6 +251,8 @@ __global__ __launch_bounds__(128) void lower_trees(
       konst = form == 2;
     } else if (op == OP_SIN || op == OP_COS) {
       ++n_trig;
+    } else if (op == OP_ABS || op == OP_SQRT) {
+      n_div += op == OP_SQRT;           // (priced like a division, below)
     } else if (op == OP_NOT || op == OP_ITE) {
       ok = false;
     }
@@ -495,6 +497,14 @@ std::string validate_program(const uint32_t* w, int64_t n, int machine,
     } else if (op == OP_NEG || op == OP_SIN || op == OP_COS) {
       if (!F) return "float opcode on the boolean machine";
       if (op != OP_NEG && n_trig) ++*n_trig;
+    } else if (op == OP_ABS || op == OP_SQRT) {
+      // abs (index field 1: math.fabs, read by the exact pass only) and the
+      // correctly rounded sqrt: asm-capable (the fp64 and fp32 cores' ABS /
+      // SQRT handlers; the typed core has none: typed_runs declines them).
+      // The planner counts a sqrt like a division (an unmeasured weight)
+      if (!F) return "float opcode on the boolean machine";
+      if (x > (op == OP_ABS ? 1u : 0u)) return "bad index field of abs / sqrt";
+      if (op == OP_SQRT && n_div) ++*n_div;
     } else if (op == OP_NOT) {
       ok = false;
     } else if (op == OP_ITE) {
@@ -529,6 +539,7 @@ struct CoreIds {
   // small, midlo, wide; midlo is a cos class, its sin entry is SIN_MID); the
   // cores without specialised bodies alias SIN / COS there
   int H_TRIG[trig_ranges::kClasses][2] = {{-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}};
+  int H_ABS = -1, H_SQRT = -1;      // every core but the typed one
 };
 #define CORE_IDS(NS)                                                          \
   CoreIds {                                                                   \
@@ -552,9 +563,23 @@ static_assert(asmcore::H_SIN_MID == asmcore::H_COS + 1 &&
                   asmcore32::H_COS_WIDE == asmcore::H_COS_WIDE &&
                   asmcore32_deep::H_COS_WIDE == asmcore_deep::H_COS_WIDE,
               "the range-specialised sin/cos ids follow COS in every core's layout");
-constexpr CoreIds kIds = CORE_IDS(asmcore);
-constexpr CoreIds kIdsDeep = CORE_IDS(asmcore_deep);
-constexpr CoreIds kIdsExactDeep = CORE_IDS(asmcore_exact_deep);
+#define CORE_IDS_F(NS)              \
+  [] {                              \
+    CoreIds c = CORE_IDS(NS);       \
+    c.H_ABS = NS::H_ABS;            \
+    c.H_SQRT = NS::H_SQRT;          \
+    return c;                       \
+  }()
+constexpr CoreIds kIds = CORE_IDS_F(asmcore);
+constexpr CoreIds kIdsDeep = CORE_IDS_F(asmcore_deep);
+constexpr CoreIds kIdsExactDeep = CORE_IDS_F(asmcore_exact_deep);
+static_assert(asmcore::H_ABS == asmcore::H_NEG + 1 && asmcore::H_SQRT == asmcore::H_NEG + 2 &&
+                  asmcore_exact::H_ABS == asmcore::H_ABS &&
+                  asmcore_exact::H_SQRT == asmcore::H_SQRT &&
+                  asmcore32::H_ABS == asmcore::H_ABS && asmcore32::H_SQRT == asmcore::H_SQRT &&
+                  asmcore_exact_deep::H_SQRT == asmcore_deep::H_SQRT &&
+                  asmcore32_deep::H_SQRT == asmcore_deep::H_SQRT,
+              "ABS and SQRT follow NEG in every fp64 and fp32 core's layout");
 constexpr CoreIds kIdsTyped = [] {
   CoreIds c = CORE_IDS(asmcore_typed);
   c.H_NOT = asmcore_typed::H_NOT;
@@ -680,6 +705,10 @@ HD int64_t translate_words(const uint32_t* w, const uint32_t* tab, const CoreIds
       konst = true;
     } else if (op == OP_NEG) {
       h = I.H_NEG;
+    } else if (op == OP_ABS) {
+      h = I.H_ABS;
+    } else if (op == OP_SQRT) {
+      h = I.H_SQRT;
     } else if (op == OP_SIN) {
       h = I.H_SIN;
     } else if (op == OP_COS) {
@@ -1050,10 +1079,14 @@ int init_asm(gpe_ctx* ctx) {
     out.resize(n);
     HIPCHK(hipMemcpy(out.data(), d_tab, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     HIPCHK(hipFree(d_tab));
-    // handlers are emitted in id order: offsets strictly increase (the
-    // first is 0 when the handlers start at the aligned .Lbase)
-    for (size_t i = 0; i < out.size(); ++i)
-      if (out[i] > (1u << 20) || (out[i] & 3u) || (i && out[i] <= out[i - 1]))
+    // every handler has an entry of its own inside the core (the first is 0
+    // when the handlers start at the aligned .Lbase).  Not in id order: the
+    // bodies of ABS and SQRT, ids beside NEG, lie after all the others
+    // (gen_asm.py defer_handler)
+    std::vector<uint32_t> sorted(out);
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t i = 0; i < sorted.size(); ++i)
+      if (sorted[i] > (1u << 20) || (sorted[i] & 3u) || (i && sorted[i] == sorted[i - 1]))
         return fail(ctx, GPE_E_HIP, std::string("implausible ") + what + " handler table");
     return 0;
   };
@@ -3269,40 +3302,42 @@ int gpe_tournament(gpe_ctx* ctx, const double* wvalues, int64_t n, int nobj,
 
 int gpe_math_probe(gpe_ctx* ctx, int fn, const double* x, double* y,
                    int64_t n) {
-  if (!ctx || !x || !y || n < 0 || fn < 0 || fn > 14) return GPE_E_INVALID;
+  if (!ctx || !x || !y || n < 0 || fn < 0 || fn > 18) return GPE_E_INVALID;
   HIPCHK(hipSetDevice(ctx->device));
   double *dx = nullptr, *dy = nullptr;
   uint32_t* dcode = nullptr;
   HIPCHK(hipMalloc(&dx, std::max<int64_t>(n, 1) * sizeof(double)));
   HIPCHK(hipMalloc(&dy, std::max<int64_t>(n, 1) * sizeof(double)));
   HIPCHK(hipMemcpy(dx, x, n * sizeof(double), hipMemcpyHostToDevice));
-  if (fn == 7 || fn == 8) {
+  if (fn == 7 || fn == 8 || fn == 18) {
     if (init_asm(ctx)) return GPE_E_HIP;
     uint32_t words[asmcore::WINDOW];
     for (auto& wd : words) wd = ctx->jump_vals32[asmcore::H_END];
     words[0] = ctx->jump_vals32[asmcore::H_LDV0];
-    words[1] = ctx->jump_vals32[fn == 7 ? asmcore::H_SIN : asmcore::H_COS];
+    words[1] = ctx->jump_vals32[fn == 7 ? asmcore::H_SIN : fn == 8 ? asmcore::H_COS
+                                                                   : asmcore::H_SQRT];
     HIPCHK(hipMalloc(&dcode, sizeof(words)));
     HIPCHK(hipMemcpy(dcode, words, sizeof(words), hipMemcpyHostToDevice));
     const int64_t per = asmcore32::K * 64;
     if (n)
       hipLaunchKernelGGL(asm_values32, dim3((unsigned)((n + per - 1) / per)),
                          dim3(64), per * sizeof(float), ctx->stream,
-                         ctx->d_cst32, dcode, dx, dy, n, fn == 8, nullptr);
-  } else if (fn == 13 || fn == 14) {
+                         ctx->d_cst32, dcode, dx, dy, n, fn == 18 ? 2 : fn == 8, nullptr);
+  } else if (fn == 13 || fn == 14 || fn == 17) {
     if (init_asm(ctx)) return GPE_E_HIP;
     uint32_t words[asmcore::WINDOW];
     for (auto& wd : words) wd = ctx->jump_vals_exact[asmcore::H_END];
     words[0] = ctx->jump_vals_exact[asmcore::H_LDV0];
-    words[1] = ctx->jump_vals_exact[fn == 13 ? asmcore::H_SIN : asmcore::H_COS];
+    words[1] = ctx->jump_vals_exact[fn == 13 ? asmcore::H_SIN : fn == 14 ? asmcore::H_COS
+                                                                         : asmcore::H_SQRT];
     HIPCHK(hipMalloc(&dcode, sizeof(words)));
     HIPCHK(hipMemcpy(dcode, words, sizeof(words), hipMemcpyHostToDevice));
     const int64_t per = asmcore_exact::K * 64;
     if (n)
       hipLaunchKernelGGL(asm_values_exact, dim3((unsigned)((n + per - 1) / per)),
                          dim3(64), asmcore_exact::GLIBC_LDS_BYTES + per * sizeof(double),
-                         ctx->stream, ctx->d_cst_exact, dcode, dx, dy, n, fn == 14,
-                         nullptr);
+                         ctx->stream, ctx->d_cst_exact, dcode, dx, dy, n,
+                         fn == 17 ? 2 : fn == 14, nullptr);
   } else if (fn == 5 || fn == 6) {
     if (init_asm(ctx)) return GPE_E_HIP;
     uint32_t words[asmcore::WINDOW];

@@ -23,12 +23,13 @@ enum : uint32_t {
   OP_ADD = 8, OP_SUB = 11, OP_RSUB = 14, OP_MUL = 17, OP_DIV = 20,
   OP_RDIV = 23, OP_LT = 26, OP_GT = 29, OP_EQ = 32, OP_AND = 35, OP_OR = 38,
   OP_XOR = 41, OP_NEG = 48, OP_SIN = 49, OP_COS = 50, OP_NOT = 51,
-  OP_ITE = 52, OP_NPDIV = 56, OP_RNPDIV = 59
+  OP_ITE = 52, OP_ABS = 53, OP_SQRT = 54, OP_NPDIV = 56, OP_RNPDIV = 59
 };
 // semantic codes passed from Python (flatten.py: _NATIVE_SEM)
 enum Sem : int {
   S_ADD = 0, S_SUB, S_MUL, S_PDIV, S_NEG, S_SIN, S_COS, S_AND, S_OR, S_XOR,
-  S_NOT, S_LT, S_EQ, S_ITE, S_NPDIV, S_NPSIN, S_NPCOS
+  S_NOT, S_LT, S_EQ, S_ITE, S_NPDIV, S_NPSIN, S_NPCOS,
+  S_ABS, S_FABS, S_SQRT, S_PSQRT, S_NPABS, S_NPSQRT
 };
 enum Kind : int { K_PRIM = 0, K_ARG = 1, K_CONST = 2 };
 constexpr int MAX_COMPILE_HEIGHT = 200;
@@ -153,7 +154,7 @@ LC_HD inline double prim_ib(int sem, const double* b, int n, bool* cand) {
       if (big(r)) *cand = true;
       return r;
     }
-    case S_NEG:
+    case S_NEG: case S_ABS:      // an int stays an int
       if (big(b[0])) *cand = true;
       return b[0];
     case S_PDIV:                 // the int is protectedDiv's 1; the quotient
@@ -166,8 +167,8 @@ LC_HD inline double prim_ib(int sem, const double* b, int n, bool* cand) {
       return 1.0;
     case S_ITE:
       return b[1] > b[2] ? b[1] : b[2];
-    default:                     // sin/cos (float), numpy semantics
-      return -1.0;
+    default:                     // sin/cos, fabs, sqrt, psqrt (float), numpy
+      return -1.0;               // semantics
   }
 }
 
@@ -220,6 +221,25 @@ LC_UNROLL
       if (k[0].i == INT64_MIN) return false;
       r.t = 'i'; r.i = -k[0].i;
       return true;
+    case S_ABS:                              // abs(-3) is 3, abs(True) is 1
+      if (k[0].t == 'f') { r.t = 'f'; r.f = __builtin_fabs(k[0].f); return true; }
+      if (k[0].i == INT64_MIN) return false;
+      r.t = 'i'; r.i = k[0].i < 0 ? -k[0].i : k[0].i;
+      return true;
+    case S_FABS: case S_NPABS:               // math.fabs(-3) is 3.0
+      r.t = 'f'; r.f = __builtin_fabs(k[0].as_f());
+      return true;
+    case S_SQRT: case S_NPSQRT: case S_PSQRT: {
+      // correctly rounded on both sides (IEEE sqrt), as math.sqrt; a
+      // negative argument: ValueError (numpy: nan)
+      double x = k[0].as_f();
+      if (sem == S_PSQRT) x = __builtin_fabs(x);
+      if (x < 0.0 && sem == S_SQRT) { r.err_value = true; return true; }
+      if (x < 0.0) return false;   // numpy's nan: its sign bit is the host's
+      r.t = 'f';
+      r.f = __builtin_sqrt(x);
+      return true;
+    }
     case S_SIN: case S_COS: {
       const double x = k[0].as_f();
       if (__builtin_isinf(x)) { r.err_value = true; return true; }
@@ -295,8 +315,13 @@ LC_HD inline void binary_ops(int sem, uint32_t& fwd, uint32_t& rev) {
   fwd = rev = 0xff;
 }
 
+// (S_PSQRT: two words, ABS then SQRT, written by the emitter; S_FABS: ABS
+// with index field 1, which only the exact pass reads)
 LC_HD inline uint32_t unary_op(int sem) {
   return sem == S_NEG ? OP_NEG
+       : (sem == S_ABS || sem == S_NPABS) ? OP_ABS
+       : sem == S_FABS ? (OP_ABS | (1u << 16))
+       : (sem == S_SQRT || sem == S_NPSQRT || sem == S_PSQRT) ? OP_SQRT
        : (sem == S_SIN || sem == S_NPSIN) ? OP_SIN
        : (sem == S_COS || sem == S_NPCOS) ? OP_COS : OP_NOT;
 }
@@ -389,6 +414,7 @@ struct Emitter {
       return;
     }
     if (fm && op >= OP_ADD && op < OP_XOR && (op - OP_ADD) % 3 == 0) op = fam_op(op);
+    else if (fm && (op & 0xffu) == OP_ABS) pneg = false;   // abs(-t) == abs(t), exactly
     else negate();
     *o++ = op | (d << 8);
   }
@@ -442,6 +468,7 @@ struct Emitter {
           next(1);
           child(r.kid[0], R.get(r.kid[0]), d);
         } else {
+          if (sem == S_PSQRT) plain(OP_ABS, d);
           plain(unary_op(sem), d);
           finish(ret);
         }

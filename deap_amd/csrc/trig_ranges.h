@@ -87,7 +87,8 @@ constexpr double kHuge = 1e300;         // a bound past it: tainted
 enum : uint32_t {
   W_END = 0, W_LDV = 1, W_LDC = 2, W_PUSH = 3, W_PUSHV = 4, W_PUSHC = 5,
   W_ADD = 8, W_SUB = 11, W_RSUB = 14, W_MUL = 17, W_DIV = 20, W_RDIV = 23,
-  W_LT = 26, W_NEG = 48, W_SIN = 49, W_COS = 50, W_NPDIV = 56, W_RNPDIV = 59
+  W_LT = 26, W_NEG = 48, W_SIN = 49, W_COS = 50, W_ABS = 53, W_SQRT = 54,
+  W_NPDIV = 56, W_RNPDIV = 59
 };
 
 enum State : uint8_t { TAINT = 0, CLEAN = 1, NANABLE = 2 };
@@ -119,6 +120,18 @@ TR_HD inline Iv sub(const Iv& a, const Iv& b) {       // a - b
   return mk(a.lo - b.hi, a.hi - b.lo, join(a, b));
 }
 TR_HD inline Iv neg(const Iv& a) { return mk(-a.hi, -a.lo, a.st); }
+// |a|: the sign bit cleared in every lane (a NaN stays a NaN: state kept)
+TR_HD inline Iv abs_iv(const Iv& a) {
+  if (a.st == TAINT) return taint();
+  return mk(maxd(0.0, maxd(a.lo, -a.hi)), maxd(absd(a.lo), absd(a.hi)), a.st);
+}
+// sqrt is correctly rounded, hence monotone: exact at the endpoints.  Only a
+// clean argument that cannot be negative: a negative lane gives NaN (and
+// ValueError), a nanable argument is not followed further
+TR_HD inline Iv sqrt_iv(const Iv& a) {
+  if (a.st != CLEAN || !(a.lo >= 0.0)) return taint();
+  return mk(__builtin_sqrt(a.lo), __builtin_sqrt(a.hi));
+}
 TR_HD inline Iv hull4(double p, double q, double r, double s, State st) {
   return mk(mind(mind(p, q), mind(r, s)), maxd(maxd(p, q), maxd(r, s)), st);
 }
@@ -228,6 +241,10 @@ struct Walk {
       T = K;
     } else if (op == W_NEG) {
       T = neg(T);
+    } else if (op == W_ABS) {
+      T = abs_iv(T);
+    } else if (op == W_SQRT) {
+      T = sqrt_iv(T);
     } else if (op == W_SIN || op == W_COS) {
       const int c = classify(T, op == W_COS, mode);
       base = base_class(T);

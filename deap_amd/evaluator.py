@@ -240,8 +240,8 @@ class TypedBoolHits(object):
     machine = Machine.F
     mode = _lib.GPE_MODE_HITS_BOOL
     outputs = ("hi", "err")
-    # with no exact-integer pass and no sin/cos (ValueError) no case can
-    # error: the counts alone
+    # with no exact-integer pass and no sin/cos or sqrt (ValueError) no case
+    # can error: the counts alone
     outputs_plain = ("hi",)
 
     def __init__(self, X, labels):
@@ -599,7 +599,7 @@ class GPUEvaluator(object):
         want = getattr(self.spec, "outputs", None) \
             if hasattr(self.spec, "finish_all") else None
         if want is not None and getattr(batch, "exact_pass", None) is None \
-                and not getattr(getattr(self.flattener, "spec", None), "has_trig", True):
+                and not getattr(getattr(self.flattener, "spec", None), "raises_value", True):
             want = getattr(self.spec, "outputs_plain", want)
         return want
 

@@ -111,6 +111,10 @@ class Op:
     COS = 50
     NOT = 51
     ITE = 52       # T = R[d] ? R[d+1] : T
+    # (outside the binary families' ranges 8-47 and 56-61)
+    ABS = 53       # T = |T| (sign bit cleared); index field 1: math.fabs,
+                   # which the exact pass converts to float first
+    SQRT = 54      # T = sqrt(T), correctly rounded; T < 0 -> ValueError
     # numpy-semantics protected division (examples/gp/symbreg_numpy.py:
     # 28-36): q = l / r, then inf or nan -> 1
     NPDIV = 56     # npdiv(operand, T)
@@ -166,6 +170,24 @@ def _is_np_pdiv(fn):
         return False
 
 
+def _is_psqrt(fn):
+    """A protected square root that is exactly ``math.sqrt(abs(x))``.  The
+    points rule out ``sqrt(x) if x > 0 else 0`` (-4.0), ``sqrt(abs(x) + eps)``
+    (4.0, the subnormal) and anything that is not correctly rounded."""
+    try:
+        r2 = math.sqrt(2.0)
+        tiny = 5e-324
+        pts = ((4.0, 2.0), (-4.0, 2.0), (2.0, r2), (-2.0, r2),
+               (tiny, math.sqrt(tiny)), (-tiny, math.sqrt(tiny)),
+               (1e308, math.sqrt(1e308)), (-1e308, math.sqrt(1e308)),
+               (9, 3.0))
+        z = fn(-0.0)
+        return (all(fn(x) == y for x, y in pts)
+                and z == 0.0 and math.copysign(1.0, z) == 1.0)
+    except Exception:
+        return False
+
+
 def _is_ite(fn):
     try:
         return (fn(True, "a", "b") == "a" and fn(False, "a", "b") == "b"
@@ -182,8 +204,17 @@ _KNOWN = {operator.add: "add", operator.sub: "sub", operator.mul: "mul",
           # numpy ufuncs of symbreg_numpy.py:39-45 (same IEEE arithmetic;
           # sin/cos of inf give nan instead of raising)
           np.add: "add", np.subtract: "sub", np.multiply: "mul",
-          np.negative: "neg", np.sin: "npsin", np.cos: "npcos"}
+          np.negative: "neg", np.sin: "npsin", np.cos: "npcos",
+          # abs and sqrt: IEEE-exact operations.  Python's abs keeps an int
+          # an int, math.fabs converts first; math.sqrt raises ValueError
+          # for a negative argument where numpy's gives nan
+          abs: "abs", operator.abs: "abs", math.fabs: "fabs",
+          math.sqrt: "sqrt", np.abs: "npabs", np.fabs: "npabs",
+          np.sqrt: "npsqrt"}
 TRIG = ("sin", "cos", "npsin", "npcos")
+# semantics whose run-time argument can raise ValueError per case
+_RAISES_VALUE = TRIG + ("sqrt",)
+_NUMPY_SEM = ("npdiv", "npsin", "npcos", "npabs", "npsqrt")
 
 _F_BINARY = {"add": (Op.ADD, Op.ADD), "sub": (Op.SUB, Op.RSUB),
              "mul": (Op.MUL, Op.MUL), "pdiv": (Op.DIV, Op.RDIV),
@@ -191,17 +222,23 @@ _F_BINARY = {"add": (Op.ADD, Op.ADD), "sub": (Op.SUB, Op.RSUB),
              "and": (Op.AND, Op.AND), "or": (Op.OR, Op.OR),
              "npdiv": (Op.NPDIV, Op.RNPDIV)}
 _F_UNARY = {"neg": Op.NEG, "sin": Op.SIN, "cos": Op.COS, "not": Op.NOT,
-            "npsin": Op.SIN, "npcos": Op.COS}
+            "npsin": Op.SIN, "npcos": Op.COS, "abs": Op.ABS, "fabs": Op.ABS,
+            "npabs": Op.ABS, "sqrt": Op.SQRT, "npsqrt": Op.SQRT}
 _B_BINARY = {"and": (Op.AND, Op.AND), "or": (Op.OR, Op.OR),
              "xor": (Op.XOR, Op.XOR)}
 _B_UNARY = {"not": Op.NOT}
 
-PsetSpec = namedtuple("PsetSpec", "machine prim_ops arg_index has_trig")
+# has_trig: the set holds sin/cos (their leaves may be device columns);
+# raises_value: some primitive can raise ValueError per case (sin/cos, sqrt)
+PsetSpec = namedtuple("PsetSpec",
+                      "machine prim_ops arg_index has_trig raises_value")
 
 # semantic name -> code of the native flattener (csrc/flatten_native.cpp)
 _NATIVE_SEM = {"add": 0, "sub": 1, "mul": 2, "pdiv": 3, "neg": 4, "sin": 5,
                "cos": 6, "and": 7, "or": 8, "xor": 9, "not": 10, "lt": 11,
-               "eq": 12, "ite": 13, "npdiv": 14, "npsin": 15, "npcos": 16}
+               "eq": 12, "ite": 13, "npdiv": 14, "npsin": 15, "npcos": 16,
+               "abs": 17, "fabs": 18, "sqrt": 19, "psqrt": 20, "npabs": 21,
+               "npsqrt": 22}
 
 
 def analyse_pset(pset, machine=None, adf_names=()):
@@ -224,6 +261,8 @@ def analyse_pset(pset, machine=None, adf_names=()):
             sem[name] = "pdiv"
         elif _is_ite(fn):
             sem[name] = "ite"
+        elif _is_psqrt(fn):
+            sem[name] = "psqrt"
     prims = [p for plist in pset.primitives.values() for p in plist]
     names = {p.name for p in prims} - adf_names
     missing = sorted(n for n in names if n not in sem)
@@ -242,7 +281,8 @@ def analyse_pset(pset, machine=None, adf_names=()):
         raise NotImplementedError("xor is only implemented on bit-planes")
     arg_index = {name: i for i, name in enumerate(pset.arguments)}
     prim_ops = {n: sem[n] for n in names}
-    return PsetSpec(machine, prim_ops, arg_index, bool(used & set(TRIG)))
+    return PsetSpec(machine, prim_ops, arg_index, bool(used & set(TRIG)),
+                    bool(used & set(_RAISES_VALUE)))
 
 
 class _Const(object):
@@ -351,7 +391,7 @@ def _int_bounds(root):
                 b = min(kb[0] * kb[1] if sem == "mul" else kb[0] + kb[1],
                         _BOUND_CAP)
                 need |= b > _EXACT_INT
-        elif sem == "neg":
+        elif sem in ("neg", "abs"):        # an int stays an int
             b = kb[0]
             need |= b > _EXACT_INT
         elif sem == "pdiv":
@@ -364,8 +404,8 @@ def _int_bounds(root):
             b = 1
         elif sem == "ite":
             b = max(kb[1], kb[2])
-        else:                              # sin/cos: floats; numpy semantics
-            b = -1
+        else:               # sin/cos, fabs, sqrt, psqrt: floats; numpy
+            b = -1          # semantics
         memo[key] = b
         peak = max(peak, b)
     return need, peak
@@ -496,8 +536,12 @@ class Flattener(object):
             return max(self._emit(k, d, out) for k in kids)
         if len(kids) == 1:
             top = self._emit(kids[0], d, out)
+            if sem == "psqrt":    # sqrt(abs(x)): two words for one node
+                out.append((Op.ABS, d, 0))
+                out.append((Op.SQRT, d, 0))
+                return top
             op = (_F_UNARY if self.machine == Machine.F else _B_UNARY)[sem]
-            out.append((op, d, 0))
+            out.append((op, d, 1 if sem == "fabs" else 0))
             return top
         if len(kids) == 3:        # if_then_else(cond, a, b)
             t0 = self._emit(kids[0], d, out)
@@ -560,6 +604,8 @@ class Flattener(object):
                 fam = op - Op.ADD
                 if Op.ADD <= op < Op.RSUB:
                     op = op + 3 if fam < 3 else op - 3
+                    pneg = False
+                elif op == Op.ABS:         # abs(-t) == abs(t), exactly
                     pneg = False
                 elif not Op.MUL <= op < Op.MUL + 3:    # a mul passes it on
                     words.append(Op.NEG)
@@ -820,7 +866,7 @@ class Flattener(object):
     def _python_ints(self):
         """Python-number semantics (not the numpy example's arrays, where
         ints never survive an operation)."""
-        return not any(s in ("npdiv", "npsin", "npcos")
+        return not any(s in _NUMPY_SEM
                        for s in self.spec.prim_ops.values())
 
     def exact_programs(self, trees):

@@ -467,7 +467,11 @@ int gpe_last_trig_picked(const gpe_ctx* ctx, int64_t* out);
  * the fp32 asm core, sin (9) / cos (10) of the C++ kernels; glibc_sin (11) /
  * glibc_cos (12), the restatement of the reference's libm; sin (13) /
  * cos (14) through the exact asm core (glibc's algorithm in the handler;
- * arguments it leaves to the C++ pass through glibc_sin/cos); on n host
+ * arguments it leaves to the C++ pass through glibc_sin/cos); the C++
+ * kernels' square root, fp64 (15) and fp32 of (float)x (16): IEEE, correctly
+ * rounded, nan for a negative argument; the same through the exact asm core's
+ * SQRT handler (17) and the fp32 asm core's (18), the handler's own value in
+ * every lane; on n host
  * inputs — the elementary operations whose rounding can differ from glibc.
  * Used by the parity tests to quantify ulp differences. */
 int gpe_math_probe(gpe_ctx* ctx, int fn, const double* x, double* y,

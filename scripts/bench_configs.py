@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-configuration throughput of one population evaluation (GPU), beside
 bench.py's C4 headline: BASELINE.json configs 1, 2, 3, 5 plus the numpy and
-ADF examples, at their stated sizes.  One JSON line per config:
+ADF examples, at their stated sizes, and a C4-shaped population over the set
+with abs and a protected square root (``c4_abs``).  One JSON line per config:
 
 * ``kernel_gpops``  node-evals x cases / device time of the evaluation
   kernels (HIP events on the context stream);
@@ -41,6 +42,9 @@ CONFIGS = {
     "c5_deep": ("spambase", {"n": 4601, "seed": 5}, "half", 100000, 2, 6,
                 502),
     "np": ("symbreg_numpy", {}, "half", 300, 1, 2, 318),
+    # C4's shape with abs and a protected square root in the set
+    "c4_abs": ("symreg10_abs", {"n": 65536, "seed": 2024}, "half", 16384, 4, 8,
+               2024),
 }
 
 
@@ -123,7 +127,7 @@ def measure(name, reps, keep=False):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="c1,c2,c3,c5,c5_deep,np,adf")
+    ap.add_argument("--only", default="c1,c2,c3,c5,c5_deep,np,adf,c4_abs")
     ap.add_argument("--reps", type=int, default=3)
     args = ap.parse_args()
     for name in args.only.split(","):
