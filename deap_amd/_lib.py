@@ -48,6 +48,9 @@ SIGNATURES = {
     "gpe_run": (_I, [_P, _I, _P, _P, _P, _P]),
     "gpe_run_device": (_I, [_P, _I, _P, _P, _P, _P]),
     "gpe_run_cases": (_I, [_P, _I, _P, _P, _P, _P, _P]),
+    "gpe_run_values": (_I, [_P, _P, _P]),
+    "gpe_run_values_device": (_I, [_P, _P, _P]),
+    "gpe_run_values_bits": (_I, [_P, _P]),
     "gpe_lexicase": (_I, [_P, _P, _I64, _I64, _P, _I, ctypes.c_double, _P,
                           _I64, _P, ctypes.POINTER(_I64)]),
     "gpe_set_lowering": (_I, [_P, _I, _I, _P, _I, _P, _I]),
@@ -347,6 +350,7 @@ class Context(object):
         self.device = device
         self.machine = None
         self.n_prog = 0
+        self.n_cases = 0
         # the ProgramBatch whose programs are loaded (identity; None after a
         # device lowering until its caller names the batch it built)
         self.resident = None
@@ -399,6 +403,7 @@ class Context(object):
                                            n_cases, _ptr(terms), n_terms),
                     "gpe_set_cases")
         self.machine = machine
+        self.n_cases = int(n_cases)
         self._keep = (X, terms)
 
     def set_trig_leaves(self, enable):
@@ -421,6 +426,7 @@ class Context(object):
                                            int(n_cases), _ptr(out_plane), 1),
                     "gpe_set_cases")
         self.machine = GPE_MACHINE_B
+        self.n_cases = int(n_cases)
         self._keep = (planes, out_plane)
 
     def load_programs(self, batch):
@@ -527,6 +533,41 @@ class Context(object):
                                                _ptr(hi), _ptr(lo), _ptr(err),
                                                _ptr(flags)), "gpe_run_cases")
         return cases, hi, lo, err, flags
+
+    def run_values(self, out=None):
+        """gpe_run_values → (values float64 [n_prog, n_cases], err uint64
+        [n_prog]): what each loaded program computes on each resident case
+        (NaN at an erroring case) and its first erroring case.  *out*: a
+        C-contiguous float64 array of that shape to write into."""
+        n, nc = self.n_prog, self.n_cases
+        if out is None:
+            out = np.empty((n, nc), dtype=np.float64)
+        if out.shape != (n, nc) or out.dtype != np.float64 or \
+                not out.flags.c_contiguous:
+            raise ValueError("run_values: out must be C-contiguous float64 "
+                             "[%d, %d]" % (n, nc))
+        err = np.full(n, GPE_NO_ERROR, dtype=np.uint64)
+        self._check(self.lib.gpe_run_values(self.h, _ptr(out), _ptr(err)),
+                    "gpe_run_values")
+        return out, err
+
+    def run_values_device(self, ptr, err_ptr=None):
+        """gpe_run_values_device: the kernels write float64
+        [n_prog, n_cases] at device address *ptr* (a torch tensor's
+        ``data_ptr()``) and uint64 [n_prog] first errors at *err_ptr*."""
+        self._check(self.lib.gpe_run_values_device(
+            self.h, ctypes.c_void_p(int(ptr)),
+            ctypes.c_void_p(int(err_ptr)) if err_ptr else None),
+            "gpe_run_values_device")
+
+    def run_values_bits(self):
+        """gpe_run_values_bits → uint32 [n_prog, ceil(n_cases / 32)]: the B
+        machine's result planes (pad bits 0)."""
+        n = self.n_prog
+        planes = np.zeros((n, (self.n_cases + 31) // 32), dtype=np.uint32)
+        self._check(self.lib.gpe_run_values_bits(self.h, _ptr(planes)),
+                    "gpe_run_values_bits")
+        return planes
 
     def lexicase(self, values, maximise, k, rng, mode=0, epsilon=0.0):
         """gpe_lexicase: k selections on ``values`` [n, n_cases] (None: the

@@ -4,6 +4,9 @@
 #pragma once
 
 // ====================================================================== host
+// the values kernels' jump tables (gpe_ctx::jump_v)
+enum { kJvFast = 0, kJvDeep, kJvExact, kJvExactDeep, kJvF32, kJvF32Deep, kJvCount };
+
 struct Launch {
   std::vector<int32_t> slot_prog;   // host copy
   int32_t* d_slot_prog = nullptr;
@@ -228,6 +231,7 @@ struct gpe_ctx {
   std::vector<uint32_t> asm32_table;
   float* d_cst32 = nullptr;
   int acode_prec = -1;
+  int acode_values = 0;       // ... translated for the values kernels (jump_v)
   std::vector<uint32_t> asm_table;   // handler id -> byte offset
   std::vector<uint32_t> asm_deep_table;    // ... of the deep fp64 core
   std::vector<uint32_t> asm_exact_table;   // ... of the exact core
@@ -251,6 +255,10 @@ struct gpe_ctx {
   std::vector<uint32_t> asm_typed_table, jump_asm_typed;
   std::vector<uint32_t> asm_exact_deep_table, jump_asm_exact_deep;
   uint32_t* d_jump_asm_exact_deep = nullptr;
+  // the values kernels' (f_eval_asm_values) jump words, by kJv* (each kernel
+  // holds its own copy of its core; the handler offsets are the tables above)
+  std::vector<uint32_t> jump_v[kJvCount];
+  uint32_t* d_jump_v[kJvCount] = {};
   std::vector<uint8_t> typed_ok;
   bool typed_valid = false;
   int use_typed = 1;                 // GPE_TYPED_ASM=0 disables (A/B testing)
@@ -397,6 +405,19 @@ struct gpe_ctx {
   double* d_np_leaf = nullptr;
   size_t np_leaf_cap = 0;
   int case_on = 0;
+  // a values run (gpe_run_values*): the per-case output receives each
+  // program's value, in values_dst when the caller gave a device buffer
+  // (else d_vals: d_case_out stays as gpe_lexicase(NULL) reads it);
+  // d_vscratch holds the run's hi / lo / first errors / flags, so the
+  // resident fitness (d_hi ...) stays as gpe_tournament(NULL) reads it
+  int values_on = 0;
+  void* values_dst = nullptr;
+  double* d_vals = nullptr;
+  size_t vals_cap = 0;
+  uint64_t* d_vscratch = nullptr;
+  size_t vscratch_cap = 0;
+  char* h_pin_vals = nullptr;        // pinned staging of gpe_run_values' copy back
+  size_t h_pin_vals_cap = 0;
   float ms[3] = {0, 0, 0};
   int64_t redo_programs = 0;
   int64_t redo_tiles = 0;
@@ -502,3 +523,10 @@ struct gpe_ctx {
   int redo_global = 0;               // inside gpe_run_sharded*: redo flags
                                      // are combined over the ranks
 };
+
+// where a run's kernels write per-case output (nullptr: none asked for)
+inline double* case_dst(const gpe_ctx* ctx) {
+  return !ctx->case_on ? nullptr
+         : ctx->values_on ? (double*)ctx->values_dst
+                          : ctx->d_case_out;
+}

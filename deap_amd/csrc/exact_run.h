@@ -36,10 +36,10 @@ int redo_pairs(gpe_ctx* ctx, uint32_t cnt, double* hi, double* lo,
   a.X = ctx->d_X;
   a.nv = ctx->nv;
   a.terms = ctx->d_terms;
-  a.nt = ctx->nt;
+  a.nt = ctx->values_on ? 0 : ctx->nt;      // (a values run reads no term column)
   a.n_cases = ctx->n_cases;
   a.n_units = ctx->n_cases;
-  a.case_out = ctx->case_on ? ctx->d_case_out : nullptr;
+  a.case_out = case_dst(ctx);
   a.first_err = err;
   a.flags = flags;
   const bool f32 = ctx->prec == GPE_PREC_F32;
@@ -56,6 +56,24 @@ int redo_pairs(gpe_ctx* ctx, uint32_t cnt, double* hi, double* lo,
                   : f_eval_pairs<asmcore_exact::K, kPairDepth, double>;
   HIPCHK(hipFuncSetAttribute((const void*)kern,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (ctx->values_on) {
+    // a values run: the pairs' values straight to the output, nothing to add
+    auto vkern = f32 ? f_eval_pairs_values<asmcore32::K, kPairDepth, float>
+                     : f_eval_pairs_values<asmcore_exact::K, kPairDepth, double>;
+    HIPCHK(hipFuncSetAttribute((const void*)vkern,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(vkern, dim3(cnt), dim3(64), lds, ctx->stream, a,
+                       (const uint64_t*)ctx->d_pair_sorted);
+    HIPCHK(hipGetLastError());
+    if (count) {
+      uint32_t runs = 0;
+      HIPCHK(hipMemcpyAsync(&runs, ctx->d_pair_nruns, sizeof(uint32_t),
+                            hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      ctx->redo_programs = (int64_t)runs;
+    }
+    return 0;
+  }
   hipLaunchKernelGGL(kern, dim3(cnt), dim3(64), lds, ctx->stream, a,
                      (const uint64_t*)ctx->d_pair_sorted, ctx->d_pair_part);
   HIPCHK(hipGetLastError());
@@ -95,9 +113,11 @@ int run_exact_asm(gpe_ctx* ctx, const std::vector<int32_t>& rx, double* hi,
   for (int32_t i : rx) cls[(size_t)i] = 1;
   for (int32_t i : rxd) cls[(size_t)i] = 2;
   XlateTabs T{};
-  T.tab[0] = T.tab[2] = ctx->d_jump_asm_exact;
+  // (a values run: the values kernels' copies of the cores)
+  const int v = ctx->values_on ? 1 : 0;
+  T.tab[0] = T.tab[2] = v ? ctx->d_jump_v[kJvExact] : ctx->d_jump_asm_exact;
   T.ids[0] = T.ids[2] = kIds;
-  T.tab[1] = ctx->d_jump_asm_exact_deep;
+  T.tab[1] = v ? ctx->d_jump_v[kJvExactDeep] : ctx->d_jump_asm_exact_deep;
   T.ids[1] = kIdsExactDeep;
   int rc0 = translate_device(ctx, &cls, T, false, false, &ctx->d_acode_x, &ctx->acode_x_cap,
                              &ctx->d_astart_x, &ctx->astart_x_cap, true);
@@ -234,7 +254,12 @@ int run_exact_host(gpe_ctx* ctx, int mode, const std::vector<int64_t>& ents, dou
           return;
         }
         double t = 0.0;
-        if (mode == GPE_MODE_MSE && !e) {
+        if (ctx->values_on) {
+          // a values run: float(T) itself (OverflowError past the float
+          // range), the default nan at an erroring case
+          if (!e) t = hbig::to_f(T, e);
+          if (e) t = std::numeric_limits<double>::quiet_NaN();
+        } else if (mode == GPE_MODE_MSE && !e) {
           double dlt = hbig::to_f(T, e);
           for (int q = 0; q < nt; ++q) dlt = dlt - terms[(int64_t)q * nc + c];
           if (!e) {
@@ -279,7 +304,7 @@ int run_exact_host(gpe_ctx* ctx, int mode, const std::vector<int64_t>& ents, dou
     memcpy(&bl, &sl[0], 8);
     rec.insert(rec.end(), {(uint64_t)prog, bh, bl, (uint64_t)e, (uint64_t)fl});
     if (ctx->case_on)
-      HIPCHK(hipMemcpy(ctx->d_case_out + (size_t)prog * nc, term.data(), nc * sizeof(double),
+      HIPCHK(hipMemcpy(case_dst(ctx) + (size_t)prog * nc, term.data(), nc * sizeof(double),
                        hipMemcpyHostToDevice));
   }
   if (ensure(ctx, &ctx->d_exh_rec, &ctx->exh_rec_cap, rec.size())) return GPE_E_HIP;
@@ -318,12 +343,21 @@ int run_exact(gpe_ctx* ctx, int mode, double* hi, double* lo,
     return GPE_E_HIP;
   for (int64_t i0 = 0; i0 < n; i0 += chunk) {
     const int64_t m = std::min(chunk, n - i0);
+    if (ctx->values_on) {
+      hipLaunchKernelGGL(f_eval_exact_values, dim3((unsigned)((nc + 255) / 256), (unsigned)m),
+                         dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_ex_code,
+                         (const int64_t*)ctx->d_ex_off, (const int32_t*)ctx->d_ex_progs, i0,
+                         (const uint32_t*)ctx->d_ex_ints, (const double*)ctx->d_X, ctx->nv, nc,
+                         case_dst(ctx), err);
+      HIPCHK(hipGetLastError());
+      continue;
+    }
     hipLaunchKernelGGL(f_eval_exact, dim3((unsigned)((nc + 255) / 256), (unsigned)m),
                        dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_ex_code,
                        (const int64_t*)ctx->d_ex_off, (const int32_t*)ctx->d_ex_progs, i0,
                        (const uint32_t*)ctx->d_ex_ints, (const double*)ctx->d_X, ctx->nv,
                        (const double*)ctx->d_terms, ctx->nt, nc, mode, ctx->d_ex_rows,
-                       ctx->case_on ? ctx->d_case_out : nullptr, err, flags);
+                       case_dst(ctx), err, flags);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(exact_rows_sum, dim3((unsigned)m), dim3(256), 0, ctx->stream,
                        (const double*)ctx->d_ex_rows, nc, (const int32_t*)ctx->d_ex_progs,

@@ -235,7 +235,12 @@ __device__ __forceinline__ void f_stage(const Task& a, R* xs,
 // R = double: the fp64 machine (reference parity).  R = float: the fp32
 // mode — cases, targets, the tree and d*d in fp32, the sum still in fp64
 // double-double.
-template <int K, int D, int MODE, typename R, bool EXACT = false>
+// VALUES (a values run, gpe_run_values*; only it launches these
+// instantiations): each case's T itself goes to case_out (the default nan
+// where the case raises ValueError); no term column is read (the task's nt
+// is 0), nothing is squared or summed, no flags and no partials are written;
+// the first ValueError still feeds first_err.
+template <int K, int D, int MODE, typename R, bool EXACT = false, bool VALUES = false>
 __global__ __launch_bounds__(kFMaxBlock) void f_eval(Task a) {
   extern __shared__ double lds_d[];
   R* lds = (R*)lds_d;
@@ -298,6 +303,20 @@ __global__ __launch_bounds__(kFMaxBlock) void f_eval(Task a) {
       if (j + 1 < n_mine) win = a.code[off_of(j + 1) + lane];
       f_run<K, R, EXACT>(W, xs, stk, lane, T, vbits, gtab);
 
+      if constexpr (VALUES) {
+        unsigned long long verr = ~0ull;
+        FOR_K {
+          const int64_t c = case0 + k * 64;
+          if (c < a.n_cases) {
+            const bool bad = ((vbits >> k) & 1u) != 0;
+            if (bad) verr = min(verr, ((unsigned long long)c << 2) | GPE_ERR_VALUE);
+            a.case_out[(size_t)prog * a.n_cases + c] =
+                bad ? __builtin_nan("") : (double)T[k];
+          }
+        }
+        if (verr != ~0ull) atomicMin(&a.first_err[prog], verr);
+        continue;
+      }
       double hi = 0.0, lo = 0.0;
       uint32_t hits = 0;                  // HITS_BOOL: wave total (uniform)
       unsigned long long err = ~0ull;
@@ -360,7 +379,7 @@ __global__ __launch_bounds__(kFMaxBlock) void f_eval(Task a) {
       }
     }
   }
-  if (my_prog >= 0) {
+  if (!VALUES && my_prog >= 0) {
     double* p = a.part + ((size_t)blockIdx.x * a.n_slots + slot0 + lane) * 2;
     p[0] = acc_hi;
     p[1] = acc_lo;
@@ -412,8 +431,11 @@ __device__ __forceinline__ void b_run(const uint32_t* pc, const uint32_t* xs,
   }
 }
 
-template <int D>
-__global__ __launch_bounds__(kBlock) void b_eval(Task a) {
+// PLANES (gpe_run_values_bits): each program's result plane, masked to the
+// valid cases, goes to case_out read as uint32[n_prog][n_units]; no popcount,
+// no partials.
+template <int D, bool PLANES>
+__device__ __forceinline__ void b_eval_impl(const Task& a) {
   extern __shared__ uint32_t ldsw[];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -457,16 +479,30 @@ __global__ __launch_bounds__(kBlock) void b_eval(Task a) {
                               (int)(my_off >> 32), j) << 32) |
                           (uint32_t)__builtin_amdgcn_readlane((int)my_off, j));
       b_run(a.code + off, xs, stk, lane, T);
+      if constexpr (PLANES) {
+        if (wd < a.n_units)
+          ((uint32_t*)a.case_out)[(size_t)prog * a.n_units + wd] = T & vmask;
+        continue;
+      }
       uint32_t h = (uint32_t)__builtin_popcount(~(T ^ outp[lane]) & vmask);
       for (int m = 32; m >= 1; m >>= 1) h += __shfl_xor(h, m, 64);
       if (lane == j) acc += (double)h;
     }
   }
-  if (my_prog >= 0) {
+  if (!PLANES && my_prog >= 0) {
     double* p = a.part + ((size_t)blockIdx.x * a.n_slots + slot0 + lane) * 2;
     p[0] = acc;
     p[1] = 0.0;
   }
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void b_eval(Task a) {
+  b_eval_impl<D, false>(a);
+}
+template <int D>
+__global__ __launch_bounds__(kBlock) void b_eval_planes(Task a) {
+  b_eval_impl<D, true>(a);
 }
 
 // Tiny case sets (n_units <= 16 words, e.g. parity-6's 64 cases = 2 words):
@@ -476,8 +512,8 @@ __global__ __launch_bounds__(kBlock) void b_eval(Task a) {
 // P) side by side.  Per-lane program counters; the op switch diverges
 // across the wave's programs (they are cost-sorted, so their lengths are
 // close); the words are the same b_run executes.
-template <int D>
-__global__ __launch_bounds__(kBlock) void b_eval_lanes(Task a, int G) {
+template <int D, bool PLANES>
+__device__ __forceinline__ void b_eval_lanes_impl(const Task& a, int G) {
   extern __shared__ uint32_t ldsw[];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -546,6 +582,11 @@ __global__ __launch_bounds__(kBlock) void b_eval_lanes(Task a, int G) {
     const int64_t rem = a.n_cases - (int64_t)wd * 32;
     vmask = rem >= 32 ? 0xffffffffu : ((1u << rem) - 1u);
   }
+  if constexpr (PLANES) {
+    if (prog >= 0 && wd < a.n_units)
+      ((uint32_t*)a.case_out)[(size_t)prog * a.n_units + wd] = T & vmask;
+    return;
+  }
   uint32_t h = (uint32_t)__builtin_popcount(~(T ^ outp[wd]) & vmask);
   for (int m = G >> 1; m >= 1; m >>= 1) h += __shfl_xor(h, m, 64);
   if (wd == 0 && prog >= 0) {
@@ -553,6 +594,15 @@ __global__ __launch_bounds__(kBlock) void b_eval_lanes(Task a, int G) {
     p[0] = (double)h;
     p[1] = 0.0;
   }
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void b_eval_lanes(Task a, int G) {
+  b_eval_lanes_impl<D, false>(a, G);
+}
+template <int D>
+__global__ __launch_bounds__(kBlock) void b_eval_lanes_planes(Task a, int G) {
+  b_eval_lanes_impl<D, true>(a, G);
 }
 
 // Sum partials over tile groups (fixed order) and scatter to program order.

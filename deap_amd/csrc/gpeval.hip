@@ -945,6 +945,10 @@ int translate_all(gpe_ctx* ctx) {
   XlateTabs T{};
   T.tab[0] = f32 ? ctx->d_jump_asm32 : ctx->d_jump_asm;
   T.tab[1] = f32 ? ctx->d_jump_asm32_deep : ctx->d_jump_asm_deep;
+  if (ctx->values_on) {        // the values kernels' copies of the cores
+    T.tab[0] = ctx->d_jump_v[f32 ? kJvF32 : kJvFast];
+    T.tab[1] = ctx->d_jump_v[f32 ? kJvF32Deep : kJvDeep];
+  }
   T.ids[0] = kIds;
   T.ids[1] = kIdsDeep;
   T.tab[2] = T.tab[0];
@@ -955,6 +959,7 @@ int translate_all(gpe_ctx* ctx) {
   if (ensure(ctx, &ctx->d_redo, &ctx->redo_cap, (size_t)std::max<int64_t>(ctx->n_prog, 1)))
     return GPE_E_HIP;
   ctx->acode_prec = ctx->prec;
+  ctx->acode_values = ctx->values_on;
   return 0;
 }
 
@@ -1163,8 +1168,8 @@ int init_asm(gpe_ctx* ctx) {
     scratch.push_back(p);
     return p;
   };
-  auto eval_probe = [&](auto kern, bool exact, bool f32) {
-    return [&, kern, exact, f32](uint32_t* d) {
+  auto eval_probe = [&](auto kern, bool exact, bool f32, bool values = false) {
+    return [&, kern, exact, f32, values](uint32_t* d) {
       const int K = f32 ? asmcore32::K : asmcore::K;
       AsmTask t{};
       t.code = (const uint32_t*)scratch_buf(64 * sizeof(uint32_t));
@@ -1190,6 +1195,8 @@ int init_asm(gpe_ctx* ctx) {
       t.cst32 = ctx->d_cst32;
       t.redo_hi = ~0u;
       t.base_probe = d;
+      // (the values kernels' epilogue after the probe writes its tile's values)
+      if (values) t.case_out = (double*)scratch_buf(K * 64 * sizeof(double));
       const uint32_t tab = f32 ? 0u : exact ? (uint32_t)asmcore_exact::GLIBC_LDS_BYTES
                                             : kTrigLdsBytes;
       const size_t lds = tab + 2 * K * 64 * (f32 ? sizeof(float) : sizeof(double)) +
@@ -1211,6 +1218,19 @@ int init_asm(gpe_ctx* ctx) {
                   ctx->jump_asm32, "fp32 asm")) ||
       (rc = jumps(eval_probe(f_eval_asm<true, true>, false, true), ctx->asm32_deep_table,
                   ctx->jump_asm32_deep, "deep fp32 asm")) ||
+      (rc = jumps(eval_probe(f_eval_asm_values<false, false>, false, false, true),
+                  ctx->asm_table, ctx->jump_v[kJvFast], "values asm")) ||
+      (rc = jumps(eval_probe(f_eval_asm_values<false, true>, false, false, true),
+                  ctx->asm_deep_table, ctx->jump_v[kJvDeep], "values deep asm")) ||
+      (rc = jumps(eval_probe(f_eval_asm_values<false, false, true>, true, false, true),
+                  ctx->asm_exact_table, ctx->jump_v[kJvExact], "values exact asm")) ||
+      (rc = jumps(eval_probe(f_eval_asm_values<false, true, true>, true, false, true),
+                  ctx->asm_exact_deep_table, ctx->jump_v[kJvExactDeep],
+                  "values exact deep asm")) ||
+      (rc = jumps(eval_probe(f_eval_asm_values<true, false>, false, true, true),
+                  ctx->asm32_table, ctx->jump_v[kJvF32], "values fp32 asm")) ||
+      (rc = jumps(eval_probe(f_eval_asm_values<true, true>, false, true, true),
+                  ctx->asm32_deep_table, ctx->jump_v[kJvF32Deep], "values deep fp32 asm")) ||
       (rc = jumps([&](uint32_t* d) {
                     constexpr int K = asmcore_typed::K;
                     AsmTask t{};
@@ -1274,6 +1294,8 @@ int init_asm(gpe_ctx* ctx) {
       upload(ctx->jump_asm_typed, &ctx->d_jump_asm_typed) ||
       upload(ctx->jump_asm_exact_deep, &ctx->d_jump_asm_exact_deep))
     return GPE_E_HIP;
+  for (int k = 0; k < kJvCount; ++k)
+    if (upload(ctx->jump_v[k], &ctx->d_jump_v[k])) return GPE_E_HIP;
   ctx->asm_ready = true;
   return 0;
 }
@@ -1281,10 +1303,15 @@ int init_asm(gpe_ctx* ctx) {
 // Build the launch plans for `mode`: MSE on the F machine sends eligible
 // programs through the asm core, everything else through the C++ kernels.
 int plan_mode(gpe_ctx* ctx, int mode) {
-  if (ctx->planned_mode == mode) return 0;
   const bool asm_mode = ctx->machine == GPE_MACHINE_F && mode == GPE_MODE_MSE &&
                         ctx->use_asm && ctx->asm_ready;
-  if (asm_mode && ctx->acode_prec != ctx->prec) {
+  // the threaded code holds handler addresses of the kernels that run it: a
+  // values run's kernels are not a fitness run's, so the first run of either
+  // kind after the other translates (and plans) again
+  const bool xlate = asm_mode && (ctx->acode_prec != ctx->prec ||
+                                  ctx->acode_values != ctx->values_on);
+  if (ctx->planned_mode == mode && !xlate) return 0;
+  if (xlate) {
     int rc0 = translate_all(ctx);
     if (rc0) return rc0;
   }
@@ -1416,7 +1443,8 @@ int run_common(gpe_ctx* ctx, int mode, double* hi, double* lo,
     return fail(ctx, GPE_E_INVALID, "HITS_BITS needs the B machine");
   if (!F && mode != GPE_MODE_HITS_BITS)
     return fail(ctx, GPE_E_INVALID, "the B machine only supports HITS_BITS");
-  if (F && mode == GPE_MODE_MSE && ctx->nt < 1)
+  // (a values run forms no term: it reads no target column)
+  if (F && mode == GPE_MODE_MSE && ctx->nt < 1 && !ctx->values_on)
     return fail(ctx, GPE_E_INVALID, "MSE needs at least one target term");
   int rc;
   ctx->last_mode = -1;         // the entry points re-validate on success
@@ -1761,13 +1789,16 @@ void gpe_destroy(gpe_ctx* ctx) {
                   ctx->d_jump_asm, ctx->d_jump_asm_deep, ctx->d_jump_asm_exact,
                   ctx->d_jump_asm32, ctx->d_jump_asm32_deep, ctx->d_jump_asm_typed,
                   ctx->d_jump_asm_exact_deep, ctx->d_redo_nsel, ctx->d_kc, ctx->d_exh_rec,
-                  ctx->d_col_bnd, ctx->d_trig_cls};
+                  ctx->d_col_bnd, ctx->d_trig_cls, ctx->d_vals, ctx->d_vscratch,
+                  ctx->d_jump_v[0], ctx->d_jump_v[1], ctx->d_jump_v[2], ctx->d_jump_v[3],
+                  ctx->d_jump_v[4], ctx->d_jump_v[5]};
   if (ctx->comm && rccl().ok) (void)rccl().comm_destroy(ctx->comm);
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
   if (ctx->h_pin_in) (void)hipHostFree(ctx->h_pin_in);
   if (ctx->h_pin_redo) (void)hipHostFree(ctx->h_pin_redo);
+  if (ctx->h_pin_vals) (void)hipHostFree(ctx->h_pin_vals);
   for (LowerChunk& C : ctx->lw_ch) {
     for (void* b : std::initializer_list<void*>{C.codes, C.node_off, C.eph_off, C.evals, C.l16,
                                                  C.rec, C.stk, C.cv, C.ib, C.words, C.wrow,
@@ -2623,6 +2654,102 @@ int gpe_run_cases(gpe_ctx* ctx, int mode, double* out_cases, double* out_hi,
   const size_t np = (size_t)ctx->n_prog;
   if (int rc_d = results_to_host(ctx, np, out_hi, out_lo, out_err, out_flags)) return rc_d;
   return 0;
+}
+
+namespace {
+// A values run: the loaded programs over the loaded cases with the per-case
+// output `dst` receiving each program's value (F: double[n_prog][n_cases],
+// the MSE plan and its kernels' values epilogues; B: uint32[n_prog][n_units],
+// the planes kernels) and `err` each program's first erroring case.  The
+// run's sums and flags go to scratch and the resident fitness
+// (gpe_tournament(NULL)'s d_hi ..., last_mode) is left as it was.
+int run_values(gpe_ctx* ctx, int machine, void* dst, unsigned long long* err) {
+  const size_t n = (size_t)ctx->n_prog;
+  // scratch: hi | lo | err | flags, 8-byte entries
+  if (ensure(ctx, &ctx->d_vscratch, &ctx->vscratch_cap, 4 * n)) return GPE_E_HIP;
+  double* hi = (double*)ctx->d_vscratch;
+  double* lo = hi + n;
+  unsigned long long* e = err ? err : (unsigned long long*)(ctx->d_vscratch + 2 * n);
+  uint32_t* flags = (uint32_t*)(ctx->d_vscratch + 3 * n);
+  const int keep_mode = ctx->last_mode;
+  ctx->values_on = 1;
+  ctx->case_on = 1;
+  ctx->values_dst = dst;
+  const int rc = run_common(ctx, machine == GPE_MACHINE_F ? GPE_MODE_MSE : GPE_MODE_HITS_BITS,
+                            hi, lo, e, flags);
+  ctx->values_on = 0;
+  ctx->case_on = 0;
+  ctx->values_dst = nullptr;
+  ctx->last_mode = keep_mode;
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+int values_check(gpe_ctx* ctx, int machine, const void* out) {
+  if (ctx->machine != machine)
+    return fail(ctx, GPE_E_INVALID, machine == GPE_MACHINE_F
+                                        ? "gpe_run_values needs the F machine"
+                                        : "gpe_run_values_bits needs the B machine");
+  if (ctx->n_prog <= 0) return fail(ctx, GPE_E_INVALID, "values run: no programs loaded");
+  if (!out) return fail(ctx, GPE_E_INVALID, "values run: null output");
+  return 0;
+}
+
+// device -> pinned staging -> the caller's (pageable) array, in pieces of at
+// most 32 MiB (as results_to_host: no pageable array is pinned in place)
+int values_to_host(gpe_ctx* ctx, void* out, const void* d_src, size_t bytes) {
+  const size_t piece = (size_t)32 << 20;
+  char* stage = pinned_buf(&ctx->h_pin_vals, &ctx->h_pin_vals_cap, std::min(bytes, piece));
+  if (!stage) return fail(ctx, GPE_E_HIP, "hipHostMalloc (values)");
+  for (size_t at = 0; at < bytes; at += piece) {
+    const size_t m = std::min(piece, bytes - at);
+    HIPCHK(hipMemcpyAsync(stage, (const char*)d_src + at, m, hipMemcpyDeviceToHost,
+                          ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const int nth = m >= ((size_t)4 << 20) ? host_threads() : 1;
+    auto copy = [&](int t) {
+      const size_t a = m * t / nth, b = m * (t + 1) / nth;
+      if (b > a) std::memcpy((char*)out + at + a, stage + a, b - a);
+    };
+    if (nth == 1) {
+      copy(0);
+    } else {
+      hostpool::par_run(nth, copy);
+    }
+  }
+  return 0;
+}
+}  // namespace
+
+int gpe_run_values_device(gpe_ctx* ctx, void* d_values, void* d_err) {
+  if (!ctx) return GPE_E_INVALID;
+  if (int rc = values_check(ctx, GPE_MACHINE_F, d_values)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  return run_values(ctx, GPE_MACHINE_F, d_values, (unsigned long long*)d_err);
+}
+
+int gpe_run_values(gpe_ctx* ctx, double* out_values, uint64_t* out_err) {
+  if (!ctx) return GPE_E_INVALID;
+  if (int rc = values_check(ctx, GPE_MACHINE_F, out_values)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t np = (size_t)ctx->n_prog, n = np * (size_t)ctx->n_cases;
+  if (ensure(ctx, &ctx->d_vals, &ctx->vals_cap, n)) return GPE_E_HIP;
+  if (int rc = run_values(ctx, GPE_MACHINE_F, ctx->d_vals, nullptr)) return rc;
+  if (int rc = values_to_host(ctx, out_values, ctx->d_vals, n * sizeof(double))) return rc;
+  if (out_err)
+    return values_to_host(ctx, out_err, ctx->d_vscratch + 2 * np, np * sizeof(uint64_t));
+  return 0;
+}
+
+int gpe_run_values_bits(gpe_ctx* ctx, uint32_t* out_planes) {
+  if (!ctx) return GPE_E_INVALID;
+  if (int rc = values_check(ctx, GPE_MACHINE_B, out_planes)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t words = (size_t)ctx->n_prog * (size_t)ctx->n_units;
+  if (ensure(ctx, &ctx->d_vals, &ctx->vals_cap, (words + 1) / 2)) return GPE_E_HIP;
+  if (int rc = run_values(ctx, GPE_MACHINE_B, ctx->d_vals, nullptr)) return rc;
+  return values_to_host(ctx, out_planes, ctx->d_vals, words * sizeof(uint32_t));
 }
 
 int gpe_eval(gpe_ctx* ctx, int mode, const uint32_t* code, int64_t n_words,

@@ -320,13 +320,13 @@ int launch_f(gpe_ctx* ctx, Launch& L, bool deep, unsigned long long* err,
   a.X = ctx->d_X;
   a.nv = ctx->nv;
   a.terms = ctx->d_terms;
-  a.nt = ctx->nt;
+  a.nt = ctx->values_on ? 0 : ctx->nt;      // (a values run reads no term column)
   a.n_cases = ctx->n_cases;
   a.n_units = ctx->n_cases;
   a.n_tiles = L.n_tiles;
   a.tiles_per_group = L.tiles_per_group;
   a.part = L.d_part;
-  a.case_out = ctx->case_on ? ctx->d_case_out : nullptr;
+  a.case_out = case_dst(ctx);
   a.first_err = err;
   a.flags = flags;
   a.sdepth = std::min(L.sdepth, D);
@@ -337,6 +337,9 @@ int launch_f(gpe_ctx* ctx, Launch& L, bool deep, unsigned long long* err,
   }
   L.lds = lds;
   auto kern = f_eval<K, D, MODE, R, EXACT>;
+  if constexpr (MODE == GPE_MODE_MSE) {
+    if (ctx->values_on) kern = f_eval<K, D, MODE, R, EXACT, true>;
+  }
   HIPCHK(hipFuncSetAttribute((const void*)kern,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   dim3 grid((unsigned)L.groups, (unsigned)(L.waves / L.wpb));
@@ -357,12 +360,13 @@ int launch_asm(gpe_ctx* ctx, Launch& L, unsigned long long* err,
   a.X = (const double*)ctx->d_X;
   a.nv = ctx->nv;
   a.terms = (const double*)ctx->d_terms;
-  a.nt = ctx->nt;
+  // (a values run reads no term column)
+  a.nt = ctx->values_on ? 0 : ctx->nt;
   a.n_cases = ctx->n_cases;
   a.n_tiles = L.n_tiles;
   a.tiles_per_group = L.tiles_per_group;
   a.part = L.d_part;
-  a.case_out = ctx->case_on ? ctx->d_case_out : nullptr;
+  a.case_out = case_dst(ctx);
   a.first_err = err;
   a.flags = flags;
   a.redo = ctx->d_redo;
@@ -392,6 +396,12 @@ int launch_asm(gpe_ctx* ctx, Launch& L, unsigned long long* err,
   auto kern = exact ? (deep_core ? f_eval_asm<false, true, true> : f_eval_asm<false, false, true>)
               : deep_core ? (f32 ? f_eval_asm<true, true> : f_eval_asm<false, true>)
                           : (f32 ? f_eval_asm<true, false> : f_eval_asm<false, false>);
+  if (ctx->values_on)          // the values kernels (their own jump tables)
+    kern = exact ? (deep_core ? f_eval_asm_values<false, true, true>
+                              : f_eval_asm_values<false, false, true>)
+           : deep_core ? (f32 ? f_eval_asm_values<true, true> : f_eval_asm_values<false, true>)
+                       : (f32 ? f_eval_asm_values<true, false>
+                              : f_eval_asm_values<false, false>);
   HIPCHK(hipFuncSetAttribute((const void*)kern,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   dim3 grid((unsigned)L.groups, (unsigned)(L.waves / L.wpb));
@@ -445,18 +455,20 @@ int launch_b(gpe_ctx* ctx, Launch& L, bool deep) {
   a.n_tiles = L.n_tiles;
   a.tiles_per_group = L.tiles_per_group;
   a.part = L.d_part;
+  const bool planes = ctx->values_on != 0;   // gpe_run_values_bits
+  if (planes) a.case_out = (double*)ctx->values_dst;   // uint32[n_prog][n_units]
   const size_t lds = lds_bytes(ctx, deep);
   L.lds = lds;
   dim3 grid((unsigned)L.groups, (unsigned)(L.waves / kWaves));
   if (G) {                                   // tiny case sets: lane-packed
-    auto kern = b_eval_lanes<D>;
+    auto kern = planes ? b_eval_lanes_planes<D> : b_eval_lanes<D>;
     HIPCHK(hipFuncSetAttribute((const void*)kern,
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, ctx->stream, a, G);
     HIPCHK(hipGetLastError());
     return 0;
   }
-  auto kern = b_eval<D>;
+  auto kern = planes ? b_eval_planes<D> : b_eval<D>;
   HIPCHK(hipFuncSetAttribute((const void*)kern,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, ctx->stream, a);
@@ -465,7 +477,8 @@ int launch_b(gpe_ctx* ctx, Launch& L, bool deep) {
 }
 
 int launch_reduce(gpe_ctx* ctx, Launch& L, double* hi, double* lo) {
-  if (L.n_slots == 0) return 0;
+  // (a values run's kernels write no partials)
+  if (L.n_slots == 0 || ctx->values_on) return 0;
   const unsigned blocks = (unsigned)((L.n_slots + 255) / 256);
   hipLaunchKernelGGL(reduce_groups, dim3(blocks), dim3(256), 0, ctx->stream,
                      L.d_part, L.n_slots, L.groups, L.d_slot_prog, hi, lo);

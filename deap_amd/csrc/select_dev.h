@@ -406,7 +406,11 @@ __global__ void clear_entries(const int32_t* progs, int64_t n,
 // error, as f_eval forms it from float(T); HITS_BOOL: the match) goes to
 // row i - i0 of `rows` (and to case_out when a per-case run asked for it).
 constexpr int kXintDepth = 32;
-__global__ __launch_bounds__(256) void f_eval_exact(
+// VALUES (a values run): case_out gets float(T) itself — an int correctly
+// rounded by to_f, OverflowError (GPE_ERR_OVERFLOW) past the float range —
+// and the default nan at an erroring case; no term, no row, no flags.
+template <bool VALUES>
+__device__ __forceinline__ void f_eval_exact_impl(
     const uint32_t* code, const int64_t* off, const int32_t* progs, int64_t i0,
     const uint32_t* ints, const double* X, int nv, const double* terms, int nt,
     int64_t n_cases, int mode, double* rows, double* case_out,
@@ -419,6 +423,13 @@ __global__ __launch_bounds__(256) void f_eval_exact(
   uint32_t err = xint::E_NONE;
   auto xv = [&](uint32_t v) { return X[(int64_t)v * n_cases + c]; };
   xint::run<kXintDepth>(code + off[li], ints, xv, T, err);
+  if constexpr (VALUES) {
+    double v = 0.0;
+    if (!err) v = xint::to_f(T, err);
+    if (err) atomicMin(&first_err[prog], ((unsigned long long)c << 2) | err);
+    case_out[(size_t)prog * n_cases + c] = err ? __builtin_nan("") : v;
+    return;
+  }
   double term = 0.0;
   if (mode == GPE_MODE_MSE && !err) {
     // (f(x) - t0 - ...)**2: an int result converts to float first
@@ -441,6 +452,22 @@ __global__ __launch_bounds__(256) void f_eval_exact(
   if (err) atomicMin(&first_err[prog], ((unsigned long long)c << 2) | err);
   rows[blockIdx.y * n_cases + c] = term;
   if (case_out) case_out[(size_t)prog * n_cases + c] = term;
+}
+
+__global__ __launch_bounds__(256) void f_eval_exact(
+    const uint32_t* code, const int64_t* off, const int32_t* progs, int64_t i0,
+    const uint32_t* ints, const double* X, int nv, const double* terms, int nt,
+    int64_t n_cases, int mode, double* rows, double* case_out,
+    unsigned long long* first_err, uint32_t* flags) {
+  f_eval_exact_impl<false>(code, off, progs, i0, ints, X, nv, terms, nt, n_cases, mode, rows,
+                           case_out, first_err, flags);
+}
+__global__ __launch_bounds__(256) void f_eval_exact_values(
+    const uint32_t* code, const int64_t* off, const int32_t* progs, int64_t i0,
+    const uint32_t* ints, const double* X, int nv, int64_t n_cases, double* case_out,
+    unsigned long long* first_err) {
+  f_eval_exact_impl<true>(code, off, progs, i0, ints, X, nv, nullptr, 0, n_cases,
+                          GPE_MODE_MSE, nullptr, case_out, first_err, nullptr);
 }
 
 // Row sums of the exact pass in a fixed order: MSE as double-double (each

@@ -47,7 +47,9 @@ def _tuples1(values, as_int):
 
 __all__ = ["SymbRegMSE", "SymbRegNumpySSE", "SymbRegSumSSE",
            "SymbRegCaseErrors", "BooleanHits",
-           "TypedBoolHits", "GPUEvaluator", "gpu_map", "pack_bitplanes"]
+           "TypedBoolHits", "GPUEvaluator", "gpu_map", "pack_bitplanes",
+           "unpack_bitplanes", "plan_predict_chunks", "first_error_cases",
+           "predict_error"]
 
 
 def _case_error(err):
@@ -200,6 +202,52 @@ def pack_bitplanes(bits):
     return words.astype(np.uint32)
 
 
+def unpack_bitplanes(planes, n_cases):
+    """The inverse of :func:`pack_bitplanes`: ``uint32[n_rows, ceil(n/32)]``
+    → ``bool[n_rows, n_cases]`` (the pad bits of the last word dropped)."""
+    planes = np.ascontiguousarray(planes, dtype=np.uint32)
+    if planes.ndim == 1:
+        planes = planes[None, :]
+    shifts = np.arange(32, dtype=np.uint32)
+    bits = (planes[:, :, None] >> shifts) & np.uint32(1)
+    return bits.reshape(planes.shape[0], -1)[:, :n_cases].astype(bool)
+
+
+# ------------------------------------------------------ predict helpers --
+def plan_predict_chunks(n, row_bytes, max_bytes):
+    """``[(lo, hi), ...]`` covering ``range(n)`` in order: as many
+    individuals per run as keep its output (``row_bytes`` each) within
+    ``max_bytes``, but at least one (a single row past the budget runs
+    alone)."""
+    per = max(1, int(max_bytes) // max(1, int(row_bytes)))
+    return [(lo, min(n, lo + per)) for lo in range(0, n, per)]
+
+
+def first_error_cases(err):
+    """``int64[n]``: each program's first erroring case from a values run's
+    error words (``(case << 2) | type``), -1 where it has none."""
+    err = np.asarray(err, dtype=np.uint64)
+    out = (err >> np.uint64(2)).astype(np.int64)
+    out[err == np.uint64(_lib.GPE_NO_ERROR)] = -1
+    return out
+
+
+def predict_error(err, offset=0):
+    """The reference's exception for the first individual (in order) whose
+    error word says a case raised, its message naming the individual
+    (``offset`` + position) and the case; None when no case raised."""
+    err = np.asarray(err, dtype=np.uint64)
+    bad = np.flatnonzero(err != np.uint64(_lib.GPE_NO_ERROR))
+    if not len(bad):
+        return None
+    i = int(bad[0])
+    exc = _case_error(err[i])
+    where = "individual %d, case %d: " % (offset + i, int(err[i]) >> 2)
+    if isinstance(exc, OverflowError):
+        return OverflowError(where + "int too large to convert to float")
+    return type(exc)(where + str(exc))
+
+
 class BooleanHits(object):
     """``(sum(func(*in_) == out for in_, out in zip(inputs, outputs)),)``
     (multiplexer.py:75, parity.py:68) on 0/1 inputs, bit-sliced."""
@@ -283,6 +331,14 @@ def trig_leaf_columns(pset_spec, spec, precision="fp64"):
     return tuple(int(v) for v in np.flatnonzero(np.isfinite(X).all(axis=1)))
 
 
+class _Rows(object):
+    """The rows of ``predict(X=...)`` as trig_leaf_columns reads a spec."""
+    machine = Machine.F
+
+    def __init__(self, X):
+        self.X = X
+
+
 def _default_device():
     return int(os.environ.get("LOCAL_RANK", "0"))
 
@@ -349,6 +405,21 @@ class GPUEvaluator(object):
         # trees per chunk of a chunked device lowering (populations larger
         # than this are read and lowered in overlapping chunks)
         self.lower_chunk = int(os.environ.get("GPE_LOWER_CHUNK", 1 << 18))
+        # predict(X=...): the sibling context holding the held-out rows, the
+        # rows it holds, and how often rows were uploaded to it
+        self._predict_ctx = None
+        self._predict_X = None
+        self._predict_leaves = False
+        self.predict_uploads = 0
+        self.last_predict_first_error = np.zeros(0, dtype=np.int64)
+
+    def close(self):
+        """Release the device contexts (the evaluator's and predict's)."""
+        if self._predict_ctx is not None:
+            self._predict_ctx.close()
+            self._predict_ctx = None
+            self._predict_X = None
+        self.ctx.close()
 
     # the evaluator is used as toolbox.evaluate
     def __call__(self, individual):
@@ -513,7 +584,7 @@ class GPUEvaluator(object):
                           "(fp64 mode keeps Python's exact ints)"
                           % len(batch.inexact), RuntimeWarning)
 
-    def _load_exact(self, batch, individuals):
+    def _load_exact(self, batch, individuals, ctx=None):
         """Programs that can compute Python ints beyond 2**53 (the batch's
         ``inexact`` candidates, decided exactly by the host flattener) are
         re-evaluated with Python-int semantics after each run
@@ -548,7 +619,7 @@ class GPUEvaluator(object):
             # kept on the batch: a reload of its programs (gpe_load_programs
             # clears the exact pass) loads the pass again (_make_resident)
             batch.exact_pass = ([cand[j] for j in idx], code, off, depth, ints)
-            self.ctx.load_exact(*batch.exact_pass)
+            (self.ctx if ctx is None else ctx).load_exact(*batch.exact_pass)
         self.stats["exact_programs"] = self.stats.get("exact_programs", 0) + len(idx)
         return len(idx)
 
@@ -642,6 +713,133 @@ class GPUEvaluator(object):
 
     def map(self, individuals):
         return _yield_until_error(self.evaluate(list(individuals)))
+
+    # ------------------------------------------------------------ predict --
+    def _predict_context(self, X):
+        """The sibling context of ``predict(X=...)``: the evaluator's
+        machine, precision and trig-leaf setting, no target column; created
+        on first use, the rows uploaded again only when they change."""
+        bits = self.spec.machine == Machine.B
+        X = np.ascontiguousarray(X, dtype=np.uint8 if bits else np.float64)
+        if X.ndim == 1:
+            X = X[None, :]
+        n_vars = self.spec.planes.shape[0] if bits else self.spec.X.shape[0]
+        if X.ndim != 2 or X.shape[0] != n_vars:
+            raise ValueError("X must be [n_vars, n_cases] with n_vars = %d"
+                             % n_vars)
+        if self._predict_X is not None and self._predict_X.shape == X.shape \
+                and np.array_equal(self._predict_X, X, equal_nan=not bits):
+            return self._predict_ctx
+        if self._predict_ctx is None:
+            self._predict_ctx = _lib.Context(self.ctx.device)
+            if self.precision == "fp32":
+                self._predict_ctx.set_precision(_lib.GPE_PREC_F32)
+        ctx = self._predict_ctx
+        if bits:
+            if not np.isin(X, (0, 1)).all():
+                raise NotImplementedError("bit-sliced evaluation needs 0/1 data")
+            planes = pack_bitplanes(X)
+            # (the B machine's cases carry an output plane; a values run
+            # never compares with it)
+            ctx.set_bitplanes(planes, np.zeros(planes.shape[1], np.uint32),
+                              X.shape[1])
+        else:
+            ctx.set_cases(_lib.GPE_MACHINE_F, X, None)
+            # sin/cos leaf columns as the evaluator's, where these rows allow
+            # them (a leaf of a column with an inf must stay in the program,
+            # which reports the ValueError); else the plain flattener
+            leaves = getattr(self.flattener, "trig_leaves", None) or ()
+            ok = set(trig_leaf_columns(self.flattener.spec, _Rows(X),
+                                       self.precision))
+            self._predict_leaves = bool(leaves) and set(leaves) <= ok
+            if self._predict_leaves:
+                ctx.set_trig_leaves(True)
+        self._predict_X = X.copy()
+        self.predict_uploads += 1
+        return ctx
+
+    def _predict_load(self, chunk, ctx):
+        """Flatten / lower *chunk* with the evaluator's own code and load it
+        (and its exact-integer pass) into *ctx*; returns the batch."""
+        if ctx is self.ctx:
+            batch = self.lower_on_device(chunk, keep=False) \
+                if self.device_lowering else None
+            if batch is None:
+                batch = self.flatten(chunk)
+            self.prepare(batch, chunk)
+            return batch
+        fl = self.flattener
+        if getattr(fl, "trig_leaves", None) and not self._predict_leaves:
+            if self._exact_flattener is None:
+                self._exact_flattener = Flattener(self.pset, self.spec.machine)
+            fl = self._exact_flattener
+        t0 = time.perf_counter()
+        batch = fl.flatten(chunk)
+        self.stats["flatten_s"] += time.perf_counter() - t0
+        self._warn_inexact(batch)
+        ctx.load_programs(batch)
+        self._load_exact(batch, chunk, ctx=ctx)
+        return batch
+
+    def predict(self, individuals, X=None, errors="raise", max_bytes=1 << 30):
+        """What each individual computes on each case:
+        ``numpy.array([[gp.compile(t, pset)(*row) for row in rows] for t in
+        individuals], dtype=float64)``, bit for bit in fp64 mode (a bool is
+        1.0 / 0.0, a Python int ``float(int)``); a :class:`BooleanHits`
+        evaluator returns ``bool[n, n_cases]``.
+
+        *X* None: the evaluator's own resident cases; else the rows to
+        predict on, ``[n_vars, n_cases]`` like the spec's, held in a sibling
+        context (uploaded again only when they change; the training cases
+        stay in place).  The individuals are evaluated in chunks whose output
+        stays within *max_bytes* (at least one individual per run).
+
+        *errors* ``"raise"``: the reference's exception of the first
+        individual (in order) with an erroring case (``ValueError`` of
+        ``math.sin(inf)`` / ``math.sqrt(-1)``, ``OverflowError`` of an int
+        past the float range), naming the individual and the case.
+        ``"nan"``: no per-case exception; every erroring case of the fp64 /
+        fp32 cores (for exact-int programs at least the first) holds NaN and
+        ``last_predict_first_error`` (``int64[n]``, -1 for none) tells an
+        error from a computed NaN.  Compile-time errors (a tree past 200
+        levels, a constant subtree that raises) are raised either way.
+
+        Out of scope: numpy-semantics specs (:class:`SymbRegNumpySSE`, whose
+        sin/cos(inf) is a value, not an error), and case-sharded or
+        population-sharded prediction (``distributed.py``)."""
+        if errors not in ("raise", "nan"):
+            raise ValueError("errors must be 'raise' or 'nan'")
+        if self.spec.mode == _lib.GPE_MODE_SSE_NUMPY:
+            raise NotImplementedError("predict: numpy-semantics specs are not "
+                                      "supported")
+        individuals = list(individuals)
+        n = len(individuals)
+        bits = self.spec.machine == Machine.B
+        ctx = self.ctx if X is None else self._predict_context(X)
+        n_cases = ctx.n_cases
+        row_bytes = ((n_cases + 31) // 32) * 4 if bits else n_cases * 8
+        out = np.empty((n, n_cases), dtype=bool if bits else np.float64)
+        first = np.full(n, -1, dtype=np.int64)
+        self.last_predict_first_error = first
+        for lo, hi in plan_predict_chunks(n, row_bytes, max_bytes):
+            chunk = individuals[lo:hi]
+            batch = self._predict_load(chunk, ctx)
+            if getattr(batch, "any_err", True):
+                for i in np.flatnonzero(batch.err).tolist():
+                    raise SyntaxError("too many nested parentheses") \
+                        if batch.err[i] == ERR_SYNTAX else batch.const_exc[i]
+            t0 = time.perf_counter()
+            if bits:
+                out[lo:hi] = unpack_bitplanes(ctx.run_values_bits(), n_cases)
+            else:
+                _, err = ctx.run_values(out=out[lo:hi])
+                first[lo:hi] = first_error_cases(err)
+                if errors == "raise":
+                    exc = predict_error(err, lo)
+                    if exc is not None:
+                        raise exc
+            self.stats["device_s"] += time.perf_counter() - t0
+        return out
 
 
 def _yield_until_error(results):

@@ -134,6 +134,35 @@ int gpe_run_device(gpe_ctx* ctx, int mode, void* d_hi, void* d_lo,
 int gpe_run_cases(gpe_ctx* ctx, int mode, double* out_cases, double* out_hi,
                   double* out_lo, uint64_t* out_err, uint32_t* out_flags);
 
+/* A values run: what each loaded program COMPUTES on each resident case,
+ * not a fitness.  out_values is a HOST array double[n_prog][n_cases]: the
+ * program's result as numpy converts it to float64 (a bool 1.0 / 0.0, an int
+ * float(int) correctly rounded; fp32 mode: the fp32 value widened).  No
+ * target column is read (the cases may have n_terms = 0), nothing is squared
+ * or summed, and GPE_ERR_OVERFLOW only means float(int) past the float
+ * range.  out_err (may be NULL): the first erroring case per program as
+ * gpe_run gives it (GPE_NO_ERROR if none); an erroring case of the fp64 /
+ * fp32 cores holds the default nan (exact-int programs: at least the first
+ * one).  F machine only.  The resident fitness that gpe_tournament(NULL) and
+ * gpe_lexicase(NULL) read is not disturbed.
+ * Replaces: [[gp.compile(t, pset)(*row) for row in rows] for t in pop], the
+ * per-case Python loop behind held-out scoring, plots and residuals. */
+int gpe_run_values(gpe_ctx* ctx, double* out_values, uint64_t* out_err);
+
+/* Same, the kernels writing straight into the caller's DEVICE buffers (e.g.
+ * torch tensors): d_values double[n_prog][n_cases], d_err uint64[n_prog] (may
+ * be NULL).
+ * Replaces: the same loop, without the host round trip. */
+int gpe_run_values_device(gpe_ctx* ctx, void* d_values, void* d_err);
+
+/* The B machine's values run: out_planes is a HOST array
+ * uint32[n_prog][ceil(n_cases / 32)], bit c % 32 of word c / 32 the program's
+ * output on case c; the bits past n_cases in the last word are 0.
+ * Replaces: [[bool(func(*row)) for row in inputs] for func in compiled]
+ * (multiplexer.py / parity.py evaluate, before the comparison with the
+ * outputs). */
+int gpe_run_values_bits(gpe_ctx* ctx, uint32_t* out_planes);
+
 /* Device lexicase selection that replays the reference's random stream:
  * selLexicase (mode 0), selEpsilonLexicase (mode 1, epsilon) and
  * selAutomaticEpsilonLexicase (mode 2; n <= 16384) of deap/tools/
