@@ -30,6 +30,7 @@ GPE_XINT_WORDS = 34
 GPE_FLAG_NONFINITE_TERM = 1
 GPE_FLAG_NAN_TERM = 2
 GPE_FLAG_INF_TERM = 4
+GPE_FLAG_MOMENT_RANGE = 8
 
 # every symbol include/gpeval.h declares, with (restype, argtypes)
 _P = ctypes.c_void_p
@@ -51,6 +52,11 @@ SIGNATURES = {
     "gpe_run_values": (_I, [_P, _P, _P]),
     "gpe_run_values_device": (_I, [_P, _P, _P]),
     "gpe_run_values_bits": (_I, [_P, _P]),
+    "gpe_run_moments": (_I, [_P, _P, _P, _P]),
+    "gpe_run_scaled": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "gpe_run_scaled_device": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "gpe_host_scaled_from_moments": (_I, [_P, _I64, _I64, _P, _P, _P, _P, _P,
+                                          _P]),
     "gpe_lexicase": (_I, [_P, _P, _I64, _I64, _P, _I, ctypes.c_double, _P,
                           _I64, _P, ctypes.POINTER(_I64)]),
     "gpe_set_lowering": (_I, [_P, _I, _I, _P, _I, _P, _I]),
@@ -105,6 +111,7 @@ SIGNATURES = {
 }
 GPE_E_INVALID = -1
 GPE_E_COMM = -5
+GPE_E_ARG = -6
 GPE_UNIQUE_ID_BYTES = 128
 
 _lib = None
@@ -168,6 +175,34 @@ def host_np_sum(rows):
     if rc != 0:
         raise GpeError("gpe_host_np_sum failed (%d)" % rc)
     return out
+
+
+def _dd(x):
+    """A (hi, lo) double-double as the float64[2] the library reads."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.shape != (2,):
+        raise ValueError("a double-double is (hi, lo)")
+    return x
+
+
+def host_scaled_from_moments(m6, n_cases, sy, syy, flags=None):
+    """Host twin of the formula gpe_run_scaled applies on the device (CPU, no
+    GPU): moments ``[n, 6]``, the target's ``Sy``, ``Syy`` as (hi, lo) →
+    ``(mse, a, b)`` float64 ``[n]``."""
+    m6 = np.ascontiguousarray(np.atleast_2d(m6), dtype=np.float64)
+    if m6.shape[1] != 6:
+        raise ValueError("moments must be [n, 6]")
+    n = m6.shape[0]
+    sy, syy = _dd(sy), _dd(syy)
+    fl = None if flags is None else \
+        np.ascontiguousarray(flags, dtype=np.uint32)
+    mse, a, b = np.zeros(n), np.zeros(n), np.zeros(n)
+    rc = load().gpe_host_scaled_from_moments(
+        _ptr(m6), n, int(n_cases), _ptr(sy), _ptr(syy),
+        None if fl is None else _ptr(fl), _ptr(mse), _ptr(a), _ptr(b))
+    if rc != 0:
+        raise GpeError("gpe_host_scaled_from_moments failed (%d)" % rc)
+    return mse, a, b
 
 
 TRIG_CLASSES = ("general", "mid", "small")
@@ -560,6 +595,44 @@ class Context(object):
             ctypes.c_void_p(int(err_ptr)) if err_ptr else None),
             "gpe_run_values_device")
 
+    def run_moments(self):
+        """gpe_run_moments → (moments float64 [n_prog, 6] = (Sf hi, lo,
+        Sff hi, lo, Sfy hi, lo), err uint64 [n_prog], flags uint32
+        [n_prog])."""
+        n = self.n_prog
+        m6 = np.zeros((n, 6), dtype=np.float64)
+        err = np.full(n, GPE_NO_ERROR, dtype=np.uint64)
+        flags = np.zeros(n, dtype=np.uint32)
+        self._check(self.lib.gpe_run_moments(self.h, _ptr(m6), _ptr(err),
+                                             _ptr(flags)), "gpe_run_moments")
+        return m6, err, flags
+
+    def run_scaled(self, sy, syy):
+        """gpe_run_scaled → (mse, a, b float64 [n_prog], err uint64, flags
+        uint32): the linear-scaling fitness of the loaded programs; *sy*,
+        *syy*: the target's sum y and sum y^2 as (hi, lo)."""
+        n = self.n_prog
+        sy, syy = _dd(sy), _dd(syy)
+        mse, a, b = np.zeros(n), np.zeros(n), np.zeros(n)
+        err = np.full(n, GPE_NO_ERROR, dtype=np.uint64)
+        flags = np.zeros(n, dtype=np.uint32)
+        if n:
+            self._check(self.lib.gpe_run_scaled(
+                self.h, _ptr(sy), _ptr(syy), _ptr(mse), _ptr(a), _ptr(b),
+                _ptr(err), _ptr(flags)), "gpe_run_scaled")
+        return mse, a, b, err, flags
+
+    def run_scaled_device(self, sy, syy, mse_ptr, a_ptr, b_ptr, err_ptr=None,
+                          flags_ptr=None):
+        """gpe_run_scaled_device: the results at device addresses (torch
+        tensors' ``data_ptr()``)."""
+        sy, syy = _dd(sy), _dd(syy)
+        self._check(self.lib.gpe_run_scaled_device(
+            self.h, _ptr(sy), _ptr(syy), *[
+                ctypes.c_void_p(int(p)) if p else None
+                for p in (mse_ptr, a_ptr, b_ptr, err_ptr, flags_ptr)]),
+            "gpe_run_scaled_device")
+
     def run_values_bits(self):
         """gpe_run_values_bits → uint32 [n_prog, ceil(n_cases / 32)]: the B
         machine's result planes (pad bits 0)."""
@@ -812,7 +885,7 @@ class Context(object):
                         list(g)))
 
     LAUNCHES = ("asm_fast", "asm_deep", "typed", "cpp_fast", "cpp_deep",
-                "fasm", "dasm")
+                "fasm", "dasm", "moments", "moments_deep")
 
     def trig_classes(self, picked=False):
         """sin/cos words of the last exact-core translation per base class

@@ -416,6 +416,38 @@ struct gpe_ctx {
   size_t vals_cap = 0;
   uint64_t* d_vscratch = nullptr;
   size_t vscratch_cap = 0;
+  // A moments run (gpe_run_moments, gpe_run_scaled*).  Programs the exact
+  // cores hold run on the moments kernels (their own copies of the cores:
+  // jump_m, [0] D = 5, [1] deep; launch plans masm, masm_deep).  The others
+  // (past 12 slots or 32 variables, exact-int programs, programs with a redo
+  // (program, tile)) take the rows route: values runs of those programs alone
+  // into d_mrows, reduced by moments_rows, in chunks whose rows fit
+  // moments_bytes (GPE_MOMENTS_MB; 16 GiB at most, allocated as far as needed).
+  // A chunk's values run plans only the programs of [sub_lo, sub_hi) that
+  // sub_mask names (empty: all of the range); outside a moments run the range
+  // is every program.
+  std::vector<uint32_t> jump_m[2];
+  uint32_t* d_jump_m[2] = {};
+  Launch masm, masm_deep;
+  size_t moments_bytes = (size_t)16 << 30;
+  int64_t sub_lo = 0, sub_hi = INT64_MAX;
+  std::vector<uint8_t> sub_mask;
+  double* d_mrows = nullptr;
+  size_t mrows_cap = 0;
+  int32_t* d_mlist = nullptr;         // a chunk's programs, for moments_rows
+  size_t mlist_cap = 0;
+  unsigned long long* d_mom_err2 = nullptr;    // the values runs' first errors (all
+  size_t mom_err2_cap = 0;                     // programs; a chunk's are copied out)
+  // per program: the six moment words, first error, flags, (mse, a, b)
+  double* d_mom = nullptr;
+  size_t mom_cap = 0;
+  unsigned long long* d_mom_err = nullptr;
+  size_t mom_err_cap = 0;
+  uint32_t* d_mom_flags = nullptr;
+  size_t mom_flags_cap = 0;
+  double* d_scaled = nullptr;
+  size_t scaled_cap = 0;
+  int64_t moments_asm = 0, moments_rows = 0;   // programs of the last run per route
   char* h_pin_vals = nullptr;        // pinned staging of gpe_run_values' copy back
   size_t h_pin_vals_cap = 0;
   float ms[3] = {0, 0, 0};

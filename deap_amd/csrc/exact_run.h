@@ -169,6 +169,59 @@ int run_exact_asm(gpe_ctx* ctx, const std::vector<int32_t>& rx, double* hi,
   return 0;
 }
 
+// The moments kernels over the programs `rx` (the exact D = 5 core) and `rxd`
+// (the exact deep core): translated for those kernels' own copies of the
+// cores, planned with three accumulator pairs per program and lane, run, and
+// reduced into out6[n_prog][6]; first errors and GPE_FLAG_MOMENT_RANGE by
+// atomics into err / flags (cleared by the caller).  A program with a
+// (program, tile) the core leaves (an inf / nan / huge sin/cos argument) is
+// appended to `rest` whole: its sums here are incomplete.
+int run_moments_asm(gpe_ctx* ctx, const std::vector<int32_t>& rx,
+                    const std::vector<int32_t>& rxd, double* out6, unsigned long long* err,
+                    uint32_t* flags, std::vector<int32_t>& rest) {
+  const int64_t n_prog = ctx->n_prog;
+  std::vector<uint8_t> cls((size_t)n_prog, 0);
+  for (const std::vector<int32_t>* v : {&rx, &rxd})
+    for (int32_t i : *v)
+      if (i < 0 || i >= n_prog)
+        return fail(ctx, GPE_E_STATE, "moments kernels: program index out of range");
+  for (int32_t i : rx) cls[(size_t)i] = 1;
+  for (int32_t i : rxd) cls[(size_t)i] = 2;
+  XlateTabs T{};
+  T.tab[0] = T.tab[2] = ctx->d_jump_m[0];
+  T.ids[0] = T.ids[2] = kIds;
+  T.tab[1] = ctx->d_jump_m[1];
+  T.ids[1] = kIdsExactDeep;
+  if (int rc0 = translate_device(ctx, &cls, T, false, false, &ctx->d_acode_x, &ctx->acode_x_cap,
+                                 &ctx->d_astart_x, &ctx->astart_x_cap, true))
+    return rc0;
+  if (ensure(ctx, &ctx->d_redo2, &ctx->redo2_cap, (size_t)n_prog)) return GPE_E_HIP;
+  HIPCHK(hipMemsetAsync(ctx->d_redo2, 0, (size_t)n_prog * sizeof(uint32_t), ctx->stream));
+  HIPCHK(hipMemsetAsync(ctx->d_redo2_count, 0, sizeof(uint32_t), ctx->stream));
+  const int64_t keep = ctx->asm_target_blocks;
+  ctx->asm_target_blocks = ctx->xasm_target_blocks;
+  int rc = plan(ctx, ctx->masm, rx, false, true, false, false, true, 3);
+  ctx->asm_target_blocks = keep;
+  if (rc) return rc;
+  if ((rc = plan(ctx, ctx->masm_deep, rxd, false, true, true, false, true, 3))) return rc;
+  if ((rc = launch_asm(ctx, ctx->masm, err, flags, false, true, true))) return rc;
+  if ((rc = launch_asm(ctx, ctx->masm_deep, err, flags, true, true, true))) return rc;
+  if ((rc = launch_reduce_moments(ctx, ctx->masm, out6))) return rc;
+  if ((rc = launch_reduce_moments(ctx, ctx->masm_deep, out6))) return rc;
+  uint32_t cnt = 0;
+  HIPCHK(hipMemcpyAsync(&cnt, ctx->d_redo2_count, sizeof(uint32_t), hipMemcpyDeviceToHost,
+                        ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (!cnt) return 0;
+  std::vector<uint32_t> flagged((size_t)n_prog);
+  HIPCHK(hipMemcpy(flagged.data(), ctx->d_redo2, n_prog * sizeof(uint32_t),
+                   hipMemcpyDeviceToHost));
+  for (const std::vector<int32_t>* v : {&rx, &rxd})
+    for (int32_t i : *v)
+      if (flagged[(size_t)i]) rest.push_back(i);
+  return 0;
+}
+
 // host twins of two_sum / dd_add (the library is built with
 // -ffp-contract=off: the same roundings as the device's)
 void h_two_sum(double a, double b, double& s, double& e) {
@@ -341,8 +394,26 @@ int run_exact(gpe_ctx* ctx, int mode, double* hi, double* lo,
       1, std::min<int64_t>({std::max<int64_t>(n, 1), 65535, ((int64_t)64 << 20) / (nc * 8)}));
   if (n > 0 && ensure(ctx, &ctx->d_ex_rows, &ctx->ex_rows_cap, (size_t)(chunk * nc)))
     return GPE_E_HIP;
-  for (int64_t i0 = 0; i0 < n; i0 += chunk) {
-    const int64_t m = std::min(chunk, n - i0);
+  // a chunked moments run (sub_lo, sub_hi): only the list's entries whose
+  // program is in the chunk, as runs of consecutive entries
+  const bool sub = ctx->sub_lo > 0 || ctx->sub_hi < ctx->n_prog || !ctx->sub_mask.empty();
+  auto in_run = [&](int64_t prog) {
+    return prog >= ctx->sub_lo && prog < ctx->sub_hi &&
+           (ctx->sub_mask.empty() || ctx->sub_mask[(size_t)prog]);
+  };
+  auto dev_prog = [&](int64_t j) {
+    return (int64_t)ctx->ex_h_progs[(size_t)ctx->ex_dev_index[(size_t)j]];
+  };
+  if (sub && (int64_t)ctx->ex_dev_index.size() < n)
+    return fail(ctx, GPE_E_STATE, "exact pass: no host index of the device list");
+  for (int64_t i0 = 0, m = 1; i0 < n; i0 += m) {
+    m = std::min(chunk, n - i0);
+    if (sub) {
+      int64_t k = 0;
+      while (k < m && in_run(dev_prog(i0 + k))) ++k;
+      m = std::max<int64_t>(k, 1);
+      if (!k) continue;                  // (entry i0 belongs to another chunk)
+    }
     if (ctx->values_on) {
       hipLaunchKernelGGL(f_eval_exact_values, dim3((unsigned)((nc + 255) / 256), (unsigned)m),
                          dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_ex_code,
@@ -372,13 +443,16 @@ int run_exact(gpe_ctx* ctx, int mode, double* hi, double* lo,
   ctx->ms[2] += ms;
   // the host half: programs with ints past the device's, and device
   // programs whose first error is the device's range end
-  std::vector<int64_t> host = ctx->ex_host;
+  std::vector<int64_t> host;
+  for (const int64_t ent : ctx->ex_host)
+    if (in_run(ctx->ex_h_progs[(size_t)ent])) host.push_back(ent);
   if (n > 0) {
     std::vector<unsigned long long> e((size_t)ctx->n_prog);
     HIPCHK(hipMemcpy(e.data(), err, e.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     for (int64_t j = 0; j < n; ++j) {
       const int64_t ent = ctx->ex_dev_index[(size_t)j];
       const unsigned long long v = e[(size_t)ctx->ex_h_progs[(size_t)ent]];
+      if (!in_run(ctx->ex_h_progs[(size_t)ent])) continue;
       if (v != ~0ull && (v & 3u) == GPE_ERR_XINT_RANGE) host.push_back(ent);
     }
   }

@@ -1,12 +1,16 @@
-// The body of f_eval_asm and f_eval_asm_values (asm_kernels.h includes this
-// file inside each of the two kernel templates, after `constexpr bool VALUES`):
-// one text, two kernels.  The fitness kernel is compiled from exactly the
+// The body of f_eval_asm, f_eval_asm_values and f_eval_asm_moments
+// (asm_kernels.h includes this file inside each of the three kernel templates,
+// after `constexpr int EPILOGUE`): one text, three kernels.  The fitness kernel is compiled from exactly the
 // text it always had (its VALUES branch is discarded), so its registers do not
 // depend on the values epilogue; each kernel holds its own copy of its core
 // and has its own jump table (init_asm).
 // F32 = false: the fp64 core (gen_asm.py); true: the fp32 core
 // (gen_asm32.py, fp32 mode).  DEEP: the cores with asmcore_deep::D stack
 // slots.  Same geometry, staging, epilogue and redo.
+  [[maybe_unused]] constexpr bool VALUES = EPILOGUE == kEpiValues;
+  [[maybe_unused]] constexpr bool MOMENTS = EPILOGUE == kEpiMoments;
+  // accumulator pairs per program and lane (moments: f, f f, f y)
+  constexpr int ACCW = MOMENTS ? 3 : 1;
   using R = typename std::conditional<F32, float, double>::type;
   // cases per lane of this kernel's core (the D = 5 fast core may hold more
   // than the deep and exact cores)
@@ -32,7 +36,7 @@
   R* const xs0 = (R*)((char*)lds + kTab);
   R* xs = xs0;
   const R* ts = xs + a.nv * K * 64;
-  double* acc = (double*)(xs0 + tile_elems * (dbuf ? 2 : 1)) + wave * a.P * 128;
+  double* acc = (double*)(xs0 + tile_elems * (dbuf ? 2 : 1)) + wave * a.P * (128 * ACCW);
   uint32_t xa = kTab + (uint32_t)lane * (uint32_t)sizeof(R);
   const int nthreads = (int)blockDim.x, nwaves = nthreads >> 6;
   // the D = 5 fp64 core with its own program loop (GP_CORE_LOOPED): the LDS
@@ -41,7 +45,7 @@
   uint32_t vts = kTab + (uint32_t)((a.nv * K * 64 + lane) * (int)sizeof(R));
   const uint32_t vacc =
       kTab + tile_bytes * (dbuf ? 2u : 1u) +
-      (uint32_t)((wave * a.P * 128 + lane) * (int)sizeof(double));
+      (uint32_t)((wave * a.P * (128 * ACCW) + lane) * (int)sizeof(double));
   if (!F32)
     for (int i = threadIdx.x; i < (int)(kTab / 8); i += nthreads)
       trig[i] = a.cst[kCstTable + i];
@@ -69,7 +73,7 @@
   int n_mine = 0;
   for (int j = 0; j < a.P; ++j)
     if (__builtin_amdgcn_readlane(my_prog, j) >= 0) n_mine = j + 1;
-  for (int j = 0; j < a.P; ++j) {
+  for (int j = 0; j < a.P * ACCW; ++j) {
     acc[(2 * j) * 64 + lane] = 0.0;
     acc[(2 * j + 1) * 64 + lane] = 0.0;
   }
@@ -78,7 +82,8 @@
   uint32_t done_mask = 0;      // fp64: this wave's programs already flagged
   // fp64 MSE with one target column and no per-case output: the lean
   // epilogue (below) on full tiles
-  const bool lean = !F32 && a.nt == 1 && a.case_out == nullptr;
+  // (a moments run: the core returns at END for every program)
+  const bool lean = !MOMENTS && !F32 && a.nt == 1 && a.case_out == nullptr;
   Task st{};
   st.X = a.X;
   st.nv = a.nv;
@@ -211,6 +216,44 @@
           }
         }
         if (verr_at != ~0ull) atomicMin(&a.first_err[prog], verr_at);
+        return;
+      }
+      if constexpr (MOMENTS) {
+        // a moments run (f_eval_asm_moments): per valid case f, f f and f y
+        // into the lane's three double-double accumulators of program j, a
+        // product with its exact low part (the build's one fused operation:
+        // -ffp-contract=off); a case with a non-finite f or |f| >= 2^500 adds
+        // nothing and raises GPE_FLAG_MOMENT_RANGE; pad lanes add nothing
+        double* const ac = acc + (size_t)(6 * j) * 64 + lane;
+        double m[6];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) m[q] = ac[q * 64];
+        unsigned long long verr_at = ~0ull;
+        uint32_t flag = 0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const int64_t c = case0 + k * 64;
+          if (c < a.n_cases) {
+            const double f = (double)T[k];
+            if ((vbits >> k) & 1u)
+              verr_at = min(verr_at, ((unsigned long long)c << 2) | GPE_ERR_VALUE);
+            if (!(__builtin_fabs(f) < 0x1p500)) {
+              flag = GPE_FLAG_MOMENT_RANGE;
+            } else {
+              const double y = (double)ts[k * 64 + lane];
+              const double ff = f * f, fy = f * y;
+              dd_add(m[0], m[1], f, 0.0);
+              dd_add(m[2], m[3], ff, __builtin_fma(f, f, -ff));
+              dd_add(m[4], m[5], fy, __builtin_fma(f, y, -fy));
+            }
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < 6; ++q) ac[q * 64] = m[q];
+        if (verr_at != ~0ull) atomicMin(&a.first_err[prog], verr_at);
+        if (__builtin_amdgcn_ballot_w64(flag != 0)) {
+          if (lane == 0) atomicOr(&a.flags[prog], GPE_FLAG_MOMENT_RANGE);
+        }
         return;
       }
       double hi = acc[(2 * j) * 64 + lane], lo = acc[(2 * j + 1) * 64 + lane];
@@ -381,9 +424,10 @@
       __syncthreads();
     }
   }
-  // one cross-lane reduction per program per tile group
+  // one cross-lane reduction per program per tile group (moments: of each
+  // of the three pairs, six words per slot)
 #pragma nounroll
-  for (int j = 0; j < n_mine; ++j) {
+  for (int j = 0; j < n_mine * ACCW; ++j) {
     double hi = acc[(2 * j) * 64 + lane], lo = acc[(2 * j + 1) * 64 + lane];
     for (int m = 32; m >= 1; m >>= 1) {
       const double ohi = shfl_xor_d(hi, m);
@@ -391,7 +435,7 @@
       dd_add(hi, lo, ohi, olo);
     }
     if (lane == 0) {
-      double* p = a.part + ((size_t)grp * a.n_slots + slot0 + j) * 2;
+      double* p = a.part + ((size_t)grp * a.n_slots * ACCW + slot0 * ACCW + j) * 2;
       p[0] = hi;
       p[1] = lo;
     }

@@ -622,6 +622,26 @@ __global__ __launch_bounds__(256) void reduce_groups(
   out_lo[prog] = lo;
 }
 
+// ... of the moments kernels' partials [group][slot][3 pairs] into the
+// programs' six moment words, the same fixed order for each pair
+__global__ __launch_bounds__(256) void reduce_groups_moments(
+    const double* part, int64_t n_slots, int n_groups, const int32_t* slot_prog,
+    double* out6) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_slots) return;
+  const int prog = slot_prog[s];
+  if (prog < 0) return;
+  for (int q = 0; q < 3; ++q) {
+    double hi = 0.0, lo = 0.0;
+    for (int g = 0; g < n_groups; ++g) {
+      const double* p = part + (((size_t)g * n_slots + s) * 3 + q) * 2;
+      dd_add(hi, lo, p[0], p[1]);
+    }
+    out6[(size_t)prog * 6 + 2 * q] = hi;
+    out6[(size_t)prog * 6 + 2 * q + 1] = lo;
+  }
+}
+
 // Diagnostic: the device's elementary functions on host-given inputs.
 __global__ void math_probe(int fn, const double* x, double* y, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

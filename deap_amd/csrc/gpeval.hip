@@ -290,6 +290,7 @@ struct U16ToI64 {
 
 }  // namespace
 #include "select_dev.h"
+#include "moments.h"
 
 #include "ctx.h"
 
@@ -1184,7 +1185,7 @@ int init_asm(gpe_ctx* ctx) {
       t.n_cases = K * 64;
       t.n_tiles = 1;
       t.tiles_per_group = 1;
-      t.part = (double*)scratch_buf(2 * sizeof(double));
+      t.part = (double*)scratch_buf(6 * sizeof(double));     // (moments: six words)
       t.first_err = (unsigned long long*)scratch_buf(sizeof(unsigned long long));
       t.flags = (uint32_t*)scratch_buf(sizeof(uint32_t));
       t.redo = (uint32_t*)scratch_buf(sizeof(uint32_t));
@@ -1200,7 +1201,7 @@ int init_asm(gpe_ctx* ctx) {
       const uint32_t tab = f32 ? 0u : exact ? (uint32_t)asmcore_exact::GLIBC_LDS_BYTES
                                             : kTrigLdsBytes;
       const size_t lds = tab + 2 * K * 64 * (f32 ? sizeof(float) : sizeof(double)) +
-                         128 * sizeof(double);
+                         3 * 128 * sizeof(double);    // (the moments kernels' accumulators)
       (void)hipFuncSetAttribute((const void*)kern,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       hipLaunchKernelGGL(kern, dim3(1, 1), dim3(64), lds, ctx->stream, t);
@@ -1231,6 +1232,10 @@ int init_asm(gpe_ctx* ctx) {
                   ctx->asm32_table, ctx->jump_v[kJvF32], "values fp32 asm")) ||
       (rc = jumps(eval_probe(f_eval_asm_values<true, true>, false, true, true),
                   ctx->asm32_deep_table, ctx->jump_v[kJvF32Deep], "values deep fp32 asm")) ||
+      (rc = jumps(eval_probe(f_eval_asm_moments<false, false, true>, true, false),
+                  ctx->asm_exact_table, ctx->jump_m[0], "moments exact asm")) ||
+      (rc = jumps(eval_probe(f_eval_asm_moments<false, true, true>, true, false),
+                  ctx->asm_exact_deep_table, ctx->jump_m[1], "moments exact deep asm")) ||
       (rc = jumps([&](uint32_t* d) {
                     constexpr int K = asmcore_typed::K;
                     AsmTask t{};
@@ -1296,6 +1301,8 @@ int init_asm(gpe_ctx* ctx) {
     return GPE_E_HIP;
   for (int k = 0; k < kJvCount; ++k)
     if (upload(ctx->jump_v[k], &ctx->d_jump_v[k])) return GPE_E_HIP;
+  for (int k = 0; k < 2; ++k)
+    if (upload(ctx->jump_m[k], &ctx->d_jump_m[k])) return GPE_E_HIP;
   ctx->asm_ready = true;
   return 0;
 }
@@ -1335,7 +1342,11 @@ int plan_mode(gpe_ctx* ctx, int mode) {
   // threads over program ranges at pop 1M: the serial pass was 1-3 ms)
   auto t_p = std::chrono::steady_clock::now();
   {
-    const int64_t n = ctx->n_prog;
+    // the programs of this run: all of them, or the chunk [sub_lo, sub_hi) of a
+    // chunked moments run (the others are in no launch list)
+    const int64_t p_lo = std::max<int64_t>(0, ctx->sub_lo);
+    const int64_t n = std::max<int64_t>(0, std::min<int64_t>(ctx->n_prog, ctx->sub_hi) - p_lo);
+    auto take = [&](int64_t i) { return ctx->sub_mask.empty() || ctx->sub_mask[(size_t)i]; };
     auto cls = [&](int64_t i) {
       if (asm_mode && ctx->asm_ok[(size_t)i] == 1) return 0;
       if (asm_mode && ctx->asm_ok[(size_t)i] == 2) return 1;
@@ -1346,7 +1357,8 @@ int plan_mode(gpe_ctx* ctx, int mode) {
     std::vector<std::array<int64_t, 6>> cnt((size_t)nth);
     hostpool::par_run(nth, [&](int t) {
       std::array<int64_t, 6> c{};
-      for (int64_t i = n * t / nth, e = n * (t + 1) / nth; i < e; ++i) ++c[(size_t)cls(i)];
+      for (int64_t i = p_lo + n * t / nth, e = p_lo + n * (t + 1) / nth; i < e; ++i)
+        if (take(i)) ++c[(size_t)cls(i)];
       cnt[(size_t)t] = c;
     });
     std::vector<int32_t>* out[6] = {&fa, &da, &ta, &fc, &dc, &kc};
@@ -1361,7 +1373,8 @@ int plan_mode(gpe_ctx* ctx, int mode) {
     }
     hostpool::par_run(nth, [&](int t) {
       std::array<int64_t, 6> at = cnt[(size_t)t];
-      for (int64_t i = n * t / nth, e = n * (t + 1) / nth; i < e; ++i) {
+      for (int64_t i = p_lo + n * t / nth, e = p_lo + n * (t + 1) / nth; i < e; ++i) {
+        if (!take(i)) continue;
         const int k = cls(i);
         (*out[k])[(size_t)at[(size_t)k]++] = (int32_t)i;
       }
@@ -1706,6 +1719,8 @@ int gpe_create(int device, gpe_ctx** out) {
   if ((env = getenv("GPE_DIV_W")) && atoi(env) >= 0 && atoi(env) <= 1000)
     ctx->div_w = atoi(env);
   if ((env = getenv("GPE_DIAG"))) ctx->diag = atoi(env);
+  if ((env = getenv("GPE_MOMENTS_MB")) && atol(env) >= 1)
+    ctx->moments_bytes = (size_t)atol(env) << 20;
   if ((env = getenv("GPE_EXACT_ALL"))) ctx->exact_all = atoi(env) != 0;
   if ((env = getenv("GPE_TRIG_RANGES")))
     ctx->trig_ranges = atoi(env) <= 0 ? trig_ranges::kOff
@@ -1791,7 +1806,11 @@ void gpe_destroy(gpe_ctx* ctx) {
                   ctx->d_jump_asm_exact_deep, ctx->d_redo_nsel, ctx->d_kc, ctx->d_exh_rec,
                   ctx->d_col_bnd, ctx->d_trig_cls, ctx->d_vals, ctx->d_vscratch,
                   ctx->d_jump_v[0], ctx->d_jump_v[1], ctx->d_jump_v[2], ctx->d_jump_v[3],
-                  ctx->d_jump_v[4], ctx->d_jump_v[5]};
+                  ctx->d_jump_v[4], ctx->d_jump_v[5], ctx->d_mrows, ctx->d_mom,
+                  ctx->d_mom_err, ctx->d_mom_flags, ctx->d_scaled, ctx->d_mom_err2,
+                  ctx->d_mlist, ctx->d_jump_m[0], ctx->d_jump_m[1],
+                  ctx->masm.d_slot_prog, ctx->masm.d_part, ctx->masm_deep.d_slot_prog,
+                  ctx->masm_deep.d_part};
   if (ctx->comm && rccl().ok) (void)rccl().comm_destroy(ctx->comm);
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -1812,7 +1831,8 @@ void gpe_destroy(gpe_ctx* ctx) {
     if (st) (void)hipStreamDestroy(st);
   if (ctx->lw_hm) (void)hipHostFree(ctx->lw_hm);
   for (Launch* L : {&ctx->fast, &ctx->deep, &ctx->fasm, &ctx->dasm, &ctx->tasm, &ctx->redo_fast,
-                    &ctx->redo_deep, &ctx->redo_xasm, &ctx->redo_xasm_deep})
+                    &ctx->redo_deep, &ctx->redo_xasm, &ctx->redo_xasm_deep, &ctx->masm,
+                    &ctx->masm_deep})
     if (L->h_pin) (void)hipHostFree(L->h_pin);
   for (auto& e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
@@ -2752,6 +2772,191 @@ int gpe_run_values_bits(gpe_ctx* ctx, uint32_t* out_planes) {
   return values_to_host(ctx, out_planes, ctx->d_vals, words * sizeof(uint32_t));
 }
 
+namespace {
+int moments_check(gpe_ctx* ctx) {
+  if (ctx->machine != GPE_MACHINE_F)
+    return fail(ctx, GPE_E_ARG, "a moments run needs the F machine");
+  if (ctx->prec != GPE_PREC_F64)
+    return fail(ctx, GPE_E_ARG, "a moments run is fp64 (the context is in fp32 mode)");
+  if (ctx->nt != 1)
+    return fail(ctx, GPE_E_ARG, "a moments run needs exactly one target column");
+  if (ctx->n_prog <= 0) return fail(ctx, GPE_E_INVALID, "moments run: no programs loaded");
+  return 0;
+}
+
+// The moments of the loaded programs into ctx->d_mom.  Programs the exact
+// cores hold run on the moments kernels (run_moments_asm: three sums per
+// program in LDS, six words per slot and tile group).  The rest take the rows
+// route: programs past 12 slots or 32 variables, exact-int programs, programs
+// the moments kernels flag for a redo (program, tile), and every program
+// where the exact cores are off (GPE_ASM=0, GPE_EXACT_ALL=0).  The rows route
+// runs its programs in chunks: a range [p0, p1) of at most `per` programs
+// whose rows fit ctx->moments_bytes, a values run of the listed programs of
+// that range alone (plan_mode's sub_lo / sub_hi / sub_mask), moments_rows on
+// them.  d_err / d_flags: device arrays of n_prog entries.
+int run_moments(gpe_ctx* ctx, unsigned long long* d_err, uint32_t* d_flags) {
+  const int64_t np = ctx->n_prog, nc = ctx->n_cases;
+  if (ensure(ctx, &ctx->d_mom, &ctx->mom_cap, 6 * (size_t)np)) return GPE_E_HIP;
+  HIPCHK(hipMemsetAsync(d_err, 0xff, (size_t)np * sizeof(unsigned long long), ctx->stream));
+  HIPCHK(hipMemsetAsync(d_flags, 0, (size_t)np * sizeof(uint32_t), ctx->stream));
+  // the two routes' programs
+  std::vector<uint8_t> rows_mask((size_t)np, 1);
+  std::vector<int32_t> rx, rxd, rest;
+  if (ctx->asm_ready && ctx->use_asm && ctx->exact_all) {
+    std::vector<uint8_t> xint((size_t)np, 0);
+    for (const int32_t p : ctx->ex_h_progs)
+      if (p >= 0 && p < np) xint[(size_t)p] = 1;
+    for (int64_t i = 0; i < np; ++i) {
+      const uint8_t c = xint[(size_t)i] ? 0 : ctx->asm_ok[(size_t)i];
+      if (c == 1) rx.push_back((int32_t)i);
+      if (c == 2) rxd.push_back((int32_t)i);
+      if (c == 1 || c == 2) rows_mask[(size_t)i] = 0;
+    }
+  }
+  ctx->masm.programs = ctx->masm_deep.programs = 0;
+  ctx->masm.lds = ctx->masm_deep.lds = 0;
+  if (!rx.empty() || !rxd.empty()) {
+    if (ctx->trig_leaves) {          // (the leaf columns, as run_common computes them)
+      const int64_t n = nc * ctx->nv_user;
+      hipLaunchKernelGGL(leaf_trig, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                         ctx->stream, (double*)ctx->d_X, ctx->nv_user, nc, 0);
+      HIPCHK(hipGetLastError());
+    }
+    if (int rc = run_moments_asm(ctx, rx, rxd, ctx->d_mom, d_err, d_flags, rest)) return rc;
+    for (const int32_t p : rest) rows_mask[(size_t)p] = 1;
+  }
+  std::vector<int32_t> list;
+  for (int64_t i = 0; i < np; ++i)
+    if (rows_mask[(size_t)i]) list.push_back((int32_t)i);
+  ctx->moments_asm = (int64_t)(rx.size() + rxd.size() - rest.size());
+  ctx->moments_rows = (int64_t)list.size();
+  if (list.empty()) return 0;
+  const int64_t per = std::max<int64_t>(
+      1, std::min<int64_t>(np, (int64_t)(ctx->moments_bytes / ((size_t)nc * sizeof(double)))));
+  if (ensure(ctx, &ctx->d_mom_err2, &ctx->mom_err2_cap, (size_t)np)) return GPE_E_HIP;
+  if (ensure(ctx, &ctx->d_mlist, &ctx->mlist_cap, list.size())) return GPE_E_HIP;
+  HIPCHK(hipMemcpyAsync(ctx->d_mlist, list.data(), list.size() * sizeof(int32_t),
+                        hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));      // (list is pageable host memory)
+  // whatever way the chunk loop is left, the next run plans every program
+  struct Whole {
+    gpe_ctx* c;
+    ~Whole() {
+      c->sub_lo = 0;
+      c->sub_hi = INT64_MAX;
+      c->sub_mask.clear();
+      c->planned_mode = -1;
+    }
+  } whole{ctx};
+  ctx->sub_mask.swap(rows_mask);
+  size_t span = 0;
+  for (size_t a = 0, b; a < list.size(); a = b) {      // widest span, for the scratch
+    for (b = a + 1; b < list.size() && list[b] - list[a] < per; ++b) {}
+    span = std::max(span, (size_t)(list[b - 1] - list[a] + 1));
+  }
+  if (ensure(ctx, &ctx->d_mrows, &ctx->mrows_cap, span * (size_t)nc)) return GPE_E_HIP;
+  for (size_t a = 0, b; a < list.size(); a = b) {
+    for (b = a + 1; b < list.size() && list[b] - list[a] < per; ++b) {}
+    const int64_t p0 = list[a], p1 = (int64_t)list[b - 1] + 1;
+    ctx->sub_lo = p0;
+    ctx->sub_hi = p1;
+    ctx->planned_mode = -1;
+    // (the values kernels index the output by program number: row p0 is rows[0];
+    // only the range's listed programs are planned, so every write is inside)
+    if (int rc = run_values(ctx, GPE_MACHINE_F, ctx->d_mrows - (size_t)p0 * (size_t)nc,
+                            ctx->d_mom_err2))
+      return rc;
+    const int64_t m = (int64_t)(b - a);
+    hipLaunchKernelGGL(copy_entries, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const int32_t*)ctx->d_mlist + a, m,
+                       (const unsigned long long*)ctx->d_mom_err2, d_err);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(moments_rows, dim3((unsigned)m), dim3(256), 0, ctx->stream,
+                       (const double*)ctx->d_mrows, nc, (const double*)ctx->d_terms, p0,
+                       (const int32_t*)ctx->d_mlist + a, ctx->d_mom, d_flags);
+    HIPCHK(hipGetLastError());
+  }
+  return 0;
+}
+
+int run_scaled(gpe_ctx* ctx, const double* sy, const double* syy, double* d_mse, double* d_a,
+               double* d_b, unsigned long long* d_err, uint32_t* d_flags) {
+  if (int rc = run_moments(ctx, d_err, d_flags)) return rc;
+  const int64_t n = ctx->n_prog;
+  hipLaunchKernelGGL(scaled_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                     ctx->d_mom, n, (double)ctx->n_cases, sy[0], sy[1], syy[0], syy[1],
+                     d_flags, d_mse, d_a, d_b);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+int moments_side_buffers(gpe_ctx* ctx) {
+  const size_t np = (size_t)ctx->n_prog;
+  if (ensure(ctx, &ctx->d_mom_err, &ctx->mom_err_cap, np)) return GPE_E_HIP;
+  if (ensure(ctx, &ctx->d_mom_flags, &ctx->mom_flags_cap, np)) return GPE_E_HIP;
+  return 0;
+}
+}  // namespace
+
+int gpe_run_moments(gpe_ctx* ctx, double* out6, uint64_t* first_err, uint32_t* flags) {
+  if (!ctx || !out6) return GPE_E_INVALID;
+  if (int rc = moments_check(ctx)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = moments_side_buffers(ctx)) return rc;
+  if (int rc = run_moments(ctx, ctx->d_mom_err, ctx->d_mom_flags)) return rc;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const size_t np = (size_t)ctx->n_prog;
+  if (int rc = values_to_host(ctx, out6, ctx->d_mom, 6 * np * sizeof(double))) return rc;
+  if (first_err)
+    if (int rc = values_to_host(ctx, first_err, ctx->d_mom_err, np * sizeof(uint64_t))) return rc;
+  if (flags)
+    if (int rc = values_to_host(ctx, flags, ctx->d_mom_flags, np * sizeof(uint32_t))) return rc;
+  return 0;
+}
+
+int gpe_run_scaled_device(gpe_ctx* ctx, const double sy[2], const double syy[2], void* d_mse,
+                          void* d_a, void* d_b, void* d_err, void* d_flags) {
+  if (!ctx || !sy || !syy || !d_mse || !d_a || !d_b) return GPE_E_INVALID;
+  if (int rc = moments_check(ctx)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = moments_side_buffers(ctx)) return rc;
+  return run_scaled(ctx, sy, syy, (double*)d_mse, (double*)d_a, (double*)d_b,
+                    d_err ? (unsigned long long*)d_err : ctx->d_mom_err,
+                    d_flags ? (uint32_t*)d_flags : ctx->d_mom_flags);
+}
+
+int gpe_run_scaled(gpe_ctx* ctx, const double sy[2], const double syy[2], double* mse, double* a,
+                   double* b, uint64_t* first_err, uint32_t* flags) {
+  if (!ctx || !sy || !syy || !mse || !a || !b) return GPE_E_INVALID;
+  if (int rc = moments_check(ctx)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = moments_side_buffers(ctx)) return rc;
+  const size_t np = (size_t)ctx->n_prog;
+  if (ensure(ctx, &ctx->d_scaled, &ctx->scaled_cap, 3 * np)) return GPE_E_HIP;
+  double* d = ctx->d_scaled;
+  if (int rc = run_scaled(ctx, sy, syy, d, d + np, d + 2 * np, ctx->d_mom_err, ctx->d_mom_flags))
+    return rc;
+  if (int rc = values_to_host(ctx, mse, d, np * sizeof(double))) return rc;
+  if (int rc = values_to_host(ctx, a, d + np, np * sizeof(double))) return rc;
+  if (int rc = values_to_host(ctx, b, d + 2 * np, np * sizeof(double))) return rc;
+  if (first_err)
+    if (int rc = values_to_host(ctx, first_err, ctx->d_mom_err, np * sizeof(uint64_t))) return rc;
+  if (flags)
+    if (int rc = values_to_host(ctx, flags, ctx->d_mom_flags, np * sizeof(uint32_t))) return rc;
+  return 0;
+}
+
+int gpe_host_scaled_from_moments(const double* m6, int64_t n, int64_t n_cases, const double sy[2],
+                                 const double syy[2], const uint32_t* flags, double* mse,
+                                 double* a, double* b) {
+  if (!m6 || n < 0 || n_cases <= 0 || !sy || !syy || !mse || !a || !b) return GPE_E_INVALID;
+  for (int64_t i = 0; i < n; ++i)
+    scaled_from_moments(m6 + i * 6, (double)n_cases, sy, syy, flags ? flags[i] : 0u, mse[i], a[i],
+                        b[i]);
+  return 0;
+}
+
 int gpe_eval(gpe_ctx* ctx, int mode, const uint32_t* code, int64_t n_words,
              const int64_t* off, int64_t n_prog, const int32_t* depth,
              double* out_hi, double* out_lo, uint64_t* out_err,
@@ -3684,6 +3889,8 @@ int gpe_last_launch_shape(const gpe_ctx* ctx, int which, int64_t* o, int n) {
     case GPE_LAUNCH_CPP_DEEP: L = &ctx->deep; break;
     case GPE_LAUNCH_FASM: L = &ctx->fasm; break;
     case GPE_LAUNCH_DASM: L = &ctx->dasm; break;
+    case GPE_LAUNCH_MOMENTS: L = &ctx->masm; break;
+    case GPE_LAUNCH_MOMENTS_DEEP: L = &ctx->masm_deep; break;
     default: return GPE_E_INVALID;
   }
   const int64_t g[GPE_LAUNCH_SHAPE_FIELDS] = {

@@ -50,8 +50,10 @@ bool asm_dbuf(const gpe_ctx* ctx, int K) {
          K * 64 * sizeof(double) == 1024;
 }
 
+// accw: accumulator pairs per program and lane (1: the fitness and values
+// kernels, 1 KiB per program per wave; 3: the moments kernels, 3 KiB)
 size_t lds_bytes_asm(const gpe_ctx* ctx, int P, int wpb, int K, bool dbuf,
-                     bool exact = false) {
+                     bool exact = false, int accw = 1) {
   const bool f32 = !exact && ctx->prec == GPE_PREC_F32 && K == asmcore32::K;
   const size_t tile = f32 ? (size_t)(ctx->nv + ctx->nt) * K * 64 * sizeof(float)
                           : (size_t)(ctx->nv + ctx->nt) * K * 64 * sizeof(double) *
@@ -59,7 +61,7 @@ size_t lds_bytes_asm(const gpe_ctx* ctx, int P, int wpb, int K, bool dbuf,
   // (f_eval_asm's kTab: the exact cores' glibc tables are half the table
   // core's, which leaves room for a sixth program per wave on C4)
   const size_t table = f32 ? 0 : exact ? (size_t)asmcore_exact::GLIBC_LDS_BYTES : kTrigLdsBytes;
-  return table + tile + (size_t)wpb * P * 128 * sizeof(double);
+  return table + tile + (size_t)wpb * P * 128 * accw * sizeof(double);
 }
 
 // B machine with at most 16 words of cases: lanes per program of the
@@ -74,7 +76,8 @@ int b_lane_group(const gpe_ctx* ctx) {
 // Balance: programs sorted by length (descending) are dealt to waves in a
 // snake order, so every wave's total work is about the mean.
 int plan(gpe_ctx* ctx, Launch& L, const std::vector<int32_t>& progs, bool deep,
-         bool is_asm, bool deep_core = false, bool typed = false, bool exact = false) {
+         bool is_asm, bool deep_core = false, bool typed = false, bool exact = false,
+         int accw = 1) {
   L.n_slots = 0;
   L.waves = 0;
   L.programs = (int64_t)progs.size();
@@ -150,7 +153,7 @@ int plan(gpe_ctx* ctx, Launch& L, const std::vector<int32_t>& progs, bool deep,
   if (is_asm && !typed) {
     auto fit = [&](bool db) {
       int P = L.P;
-      while (P > 1 && lds_bytes_asm(ctx, P, wpb, L.K, db, exact) > lds_cap) --P;
+      while (P > 1 && lds_bytes_asm(ctx, P, wpb, L.K, db, exact, accw) > lds_cap) --P;
       return P;
     };
     // the second tile buffer costs the accumulators' LDS: taken while it
@@ -160,7 +163,7 @@ int plan(gpe_ctx* ctx, Launch& L, const std::vector<int32_t>& progs, bool deep,
     const int p1 = fit(false);
     const int p2 = asm_dbuf(ctx, L.K) ? fit(true) : 0;
     L.dbuf = p2 > 0 && p2 + 2 >= p1 && (p2 >= 4 || p2 == p1) &&
-             lds_bytes_asm(ctx, p2, wpb, L.K, true, exact) <= lds_cap;
+             lds_bytes_asm(ctx, p2, wpb, L.K, true, exact, accw) <= lds_cap;
     L.P = L.dbuf ? p2 : p1;
   }
   const int64_t W = (n + L.P - 1) / L.P;
@@ -301,7 +304,7 @@ slots_done:
   HIPCHK(hipMemcpyAsync(L.d_slot_prog, slots, (size_t)L.n_slots * sizeof(int32_t),
                         hipMemcpyHostToDevice, ctx->stream));
   qlap("h2d");
-  if (ensure(ctx, &L.d_part, &L.part_cap, (size_t)L.groups * L.n_slots * 2))
+  if (ensure(ctx, &L.d_part, &L.part_cap, (size_t)L.groups * L.n_slots * 2 * accw))
     return GPE_E_HIP;
   qlap("part");
   return 0;
@@ -349,7 +352,8 @@ int launch_f(gpe_ctx* ctx, Launch& L, bool deep, unsigned long long* err,
 }
 
 int launch_asm(gpe_ctx* ctx, Launch& L, unsigned long long* err,
-               uint32_t* flags, bool deep_core = false, bool exact = false) {
+               uint32_t* flags, bool deep_core = false, bool exact = false,
+               bool moments = false) {
   if (L.n_slots == 0) return 0;
   AsmTask a{};
   a.code = exact ? ctx->d_acode_x : ctx->d_acode;
@@ -388,9 +392,9 @@ int launch_asm(gpe_ctx* ctx, Launch& L, unsigned long long* err,
   // lean, double-buffered launch)
   L.resident = exact && !deep_core && GP_ASM_LOOP_EXACT && GP_ASM_TILE_LOOP_EXACT &&
                ctx->tile_loop && L.dbuf && L.K * 64 * sizeof(double) == 1024 &&
-               a.nt == 1 && a.case_out == nullptr && a.n_tiles < (1ll << 31);
+               a.nt == 1 && a.case_out == nullptr && a.n_tiles < (1ll << 31) && !moments;
   a.tile_loop = L.resident ? 1 : 0;
-  const size_t lds = lds_bytes_asm(ctx, L.P, L.wpb, L.K, L.dbuf, exact);
+  const size_t lds = lds_bytes_asm(ctx, L.P, L.wpb, L.K, L.dbuf, exact, moments ? 3 : 1);
   L.lds = lds;
   const bool f32 = ctx->prec == GPE_PREC_F32;
   auto kern = exact ? (deep_core ? f_eval_asm<false, true, true> : f_eval_asm<false, false, true>)
@@ -402,6 +406,12 @@ int launch_asm(gpe_ctx* ctx, Launch& L, unsigned long long* err,
            : deep_core ? (f32 ? f_eval_asm_values<true, true> : f_eval_asm_values<false, true>)
                        : (f32 ? f_eval_asm_values<true, false>
                               : f_eval_asm_values<false, false>);
+  if (moments) {               // the exact cores' moments kernels (jump_m)
+    if (!exact || f32 || ctx->values_on || a.nt != 1)
+      return fail(ctx, GPE_E_STATE, "moments kernels: exact fp64 cores, one target column");
+    kern = deep_core ? f_eval_asm_moments<false, true, true>
+                     : f_eval_asm_moments<false, false, true>;
+  }
   HIPCHK(hipFuncSetAttribute((const void*)kern,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   dim3 grid((unsigned)L.groups, (unsigned)(L.waves / L.wpb));
@@ -482,6 +492,16 @@ int launch_reduce(gpe_ctx* ctx, Launch& L, double* hi, double* lo) {
   const unsigned blocks = (unsigned)((L.n_slots + 255) / 256);
   hipLaunchKernelGGL(reduce_groups, dim3(blocks), dim3(256), 0, ctx->stream,
                      L.d_part, L.n_slots, L.groups, L.d_slot_prog, hi, lo);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// the moments kernels' six words per slot and tile group into [n_prog][6]
+int launch_reduce_moments(gpe_ctx* ctx, Launch& L, double* out6) {
+  if (L.n_slots == 0) return 0;
+  const unsigned blocks = (unsigned)((L.n_slots + 255) / 256);
+  hipLaunchKernelGGL(reduce_groups_moments, dim3(blocks), dim3(256), 0, ctx->stream,
+                     L.d_part, L.n_slots, L.groups, L.d_slot_prog, out6);
   HIPCHK(hipGetLastError());
   return 0;
 }

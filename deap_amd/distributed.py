@@ -116,6 +116,10 @@ def native_comm(local):
 
 
 def _check_shardable(spec, case_sharded):
+    if getattr(spec, "scaled", False):
+        raise NotImplementedError("SymbRegScaledMSE runs on one GPU: the "
+                                  "moments are additive over case shards, "
+                                  "but no sharded moments run is built")
     if getattr(spec, "per_case", False):
         raise NotImplementedError("per-case outputs are not gathered across "
                                   "ranks; evaluate per-case specs on one GPU")

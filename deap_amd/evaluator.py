@@ -46,7 +46,8 @@ def _tuples1(values, as_int):
 
 
 __all__ = ["SymbRegMSE", "SymbRegNumpySSE", "SymbRegSumSSE",
-           "SymbRegCaseErrors", "BooleanHits",
+           "SymbRegScaledMSE", "SymbRegCaseErrors", "BooleanHits",
+           "exact_dd_sums",
            "TypedBoolHits", "GPUEvaluator", "gpu_map", "pack_bitplanes",
            "unpack_bitplanes", "plan_predict_chunks", "first_error_cases",
            "predict_error"]
@@ -170,6 +171,103 @@ class SymbRegSumSSE(SymbRegMSE):
         for i in np.flatnonzero(err != np.uint64(_lib.GPE_NO_ERROR)).tolist():
             out[i] = self.finish(i, hi[i], lo[i], err[i], flags[i])
         return out
+
+
+def _two_prod_squares(y):
+    """``(p, e)`` with ``p + e == y * y`` exactly (Dekker's product on
+    Veltkamp halves; *y* within 2**-400 .. 2**400 in magnitude, or 0)."""
+    p = y * y
+    c = 134217729.0 * y
+    yh = c - (c - y)
+    yl = y - yh
+    e = ((yh * yh - p) + yh * yl + yl * yh) + yl * yl
+    return p, e
+
+
+def exact_dd_sums(y):
+    """``((Sy hi, lo), (Syy hi, lo))``: the exact ``sum(y)`` and
+    ``sum(y * y)`` of a float64 column as double-doubles — hi the correctly
+    rounded sum (``math.fsum``), lo the correctly rounded residual."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if not np.isfinite(y).all():
+        raise ValueError("the target column must be finite")
+    vals = y.tolist()
+    sy = math.fsum(vals)
+    sy_lo = math.fsum(vals + [-sy])
+    mag = np.abs(y[y != 0.0])
+    if len(mag) and (mag.min() < 2.0 ** -400 or mag.max() > 2.0 ** 400):
+        from fractions import Fraction
+        exact = sum(Fraction(v) ** 2 for v in vals)
+        with np.errstate(over="ignore"):
+            syy = float(exact) if exact < Fraction(2) ** 1024 else math.inf
+        if math.isinf(syy):
+            raise ValueError("the target column's sum of squares overflows")
+        return (sy, sy_lo), (syy, float(exact - Fraction(syy)))
+    p, e = _two_prod_squares(y)
+    parts = p.tolist() + e.tolist()
+    syy = math.fsum(parts)
+    return (sy, sy_lo), (syy, math.fsum(parts + [-syy]))
+
+
+class SymbRegScaledMSE(SymbRegMSE):
+    """Linear-scaling fitness (Keijzer 2003): ``(mse,)`` of the best affine
+    fit ``a + b * f(x)`` to the target ``y``, from one moments run
+    (``gpe_run_scaled``).
+
+    With ``Sf = sum f``, ``Sff = sum f*f``, ``Sfy = sum f*y`` (the device's
+    double-double sums), ``Sy``, ``Syy`` (exact, from the host) and
+    ``vf = Sff - Sf**2/n``, ``vy = Syy - Sy**2/n``, ``cfy = Sfy - Sf*Sy/n``:
+    ``b = cfy/vf``, ``a = (Sy - b*Sf)/n``, ``mse = (vy - cfy**2/vf)/n``.  Two
+    rules belong to the definition: an individual with an inf, nan or
+    ``|f| >= 2**500`` output has fitness ``inf`` (``b = 0``, ``a = Sy/n``, no
+    exception), and one with ``n*vf <= 2**-40 * Sff`` counts as constant
+    (``b = 0``, ``a = Sy/n``, ``mse = vy/n``).  A case whose call raises
+    (``math.sin(inf)``, ``math.sqrt(-1)``, ``float(int)`` overflow) raises for
+    that individual, as in :class:`SymbRegMSE`.  The coefficients of the last
+    evaluation are ``GPUEvaluator.last_scaling``.
+
+    fp64, one target column, Python-semantics untyped primitive sets, one
+    GPU.  The library reduces the programs' per-case values in chunks of
+    programs that fit its scratch budget (``GPE_MOMENTS_MB``, 16 GiB)."""
+    scaled = True
+
+    def __init__(self, X, y):
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if y.ndim == 2 and y.shape[0] != 1:
+            raise ValueError("SymbRegScaledMSE takes one target column")
+        SymbRegMSE.__init__(self, X, y)
+        self.sy, self.syy = exact_dd_sums(self.terms[0])
+
+    def finish(self, i, hi, lo, err, flags):
+        if err != _lib.GPE_NO_ERROR:
+            return _case_error(err)
+        return (float(hi),)
+
+    def finish_all(self, hi, lo, err, flags):
+        out = _tuples1(hi, False)
+        for i in np.flatnonzero(err != np.uint64(_lib.GPE_NO_ERROR)).tolist():
+            out[i] = _case_error(err[i])
+        return out
+
+
+def _check_scaled_setup(spec, pset, flattener, precision):
+    """A linear-scaling spec's evaluator: what it refuses, and why."""
+    if precision == "fp32":
+        raise ValueError("SymbRegScaledMSE is fp64 only: a one-pass variance "
+                         "has no digits to spare in precision='fp32'")
+    sems = set(flattener.spec.prim_ops.values())
+    np_sems = sorted(s for s in sems if s.startswith("np"))
+    if np_sems:
+        raise NotImplementedError(
+            "SymbRegScaledMSE needs Python-semantics primitives; this set has "
+            "numpy-semantics ones (%s), whose sin/cos(inf) and division are "
+            "values, not errors" % ", ".join(np_sems))
+    for p in (pset if isinstance(pset, (list, tuple)) else [pset]):
+        if getattr(p, "ret", object) is not object:
+            raise NotImplementedError(
+                "SymbRegScaledMSE does not take a typed primitive set (%s "
+                "returns %r): the moments run covers float programs only"
+                % (getattr(p, "name", "pset"), p.ret))
 
 
 class SymbRegCaseErrors(SymbRegMSE):
@@ -372,6 +470,8 @@ class GPUEvaluator(object):
         if self.flattener.machine != spec.machine:
             raise ValueError("fitness spec and primitive set need different "
                              "machines")
+        if getattr(spec, "scaled", False):
+            _check_scaled_setup(spec, pset, self.flattener, precision)
         self.ctx = _lib.Context(_default_device() if device is None
                                 else device)
         spec.upload(self.ctx)
@@ -412,6 +512,8 @@ class GPUEvaluator(object):
         self._predict_leaves = False
         self.predict_uploads = 0
         self.last_predict_first_error = np.zeros(0, dtype=np.int64)
+        # SymbRegScaledMSE: (a, b) float64 [n] of the last evaluation
+        self.last_scaling = (np.zeros(0), np.zeros(0))
 
     def close(self):
         """Release the device contexts (the evaluator's and predict's)."""
@@ -652,7 +754,13 @@ class GPUEvaluator(object):
         t0 = time.perf_counter()
         self._make_resident(batch)
         cases = None
-        if getattr(self.spec, "per_case", False):
+        if getattr(self.spec, "scaled", False):
+            # (mse in hi's place; the coefficients beside it)
+            hi, a, b, err, flags = self.ctx.run_scaled(self.spec.sy,
+                                                       self.spec.syy)
+            lo = np.zeros_like(hi)
+            self.last_scaling = (a, b)
+        elif getattr(self.spec, "per_case", False):
             cases, hi, lo, err, flags = self.ctx.run_cases(
                 self.spec.mode, self.spec.n_cases)
         else:
@@ -781,7 +889,8 @@ class GPUEvaluator(object):
         self._load_exact(batch, chunk, ctx=ctx)
         return batch
 
-    def predict(self, individuals, X=None, errors="raise", max_bytes=1 << 30):
+    def predict(self, individuals, X=None, errors="raise", max_bytes=1 << 30,
+                scaled=False):
         """What each individual computes on each case:
         ``numpy.array([[gp.compile(t, pset)(*row) for row in rows] for t in
         individuals], dtype=float64)``, bit for bit in fp64 mode (a bool is
@@ -804,11 +913,37 @@ class GPUEvaluator(object):
         error from a computed NaN.  Compile-time errors (a tree past 200
         levels, a constant subtree that raises) are raised either way.
 
+        *scaled* True (a :class:`SymbRegScaledMSE` evaluator only, else
+        ``ValueError``): ``a[:, None] + b[:, None] * predict(...)`` with each
+        individual's coefficients fitted on the training cases — held-out
+        *X* rows are scaled by the training coefficients.  The coefficients
+        come from an evaluation of *individuals* on the training cases made
+        by this call: it counts in ``stats``, leaves ``last_scaling`` holding
+        these individuals' ``(a, b)``, and an individual whose training
+        evaluation raises has no coefficients, so its exception is raised
+        whatever *errors* says (*errors* governs the predicted rows only).
+
         Out of scope: numpy-semantics specs (:class:`SymbRegNumpySSE`, whose
         sin/cos(inf) is a value, not an error), and case-sharded or
         population-sharded prediction (``distributed.py``)."""
         if errors not in ("raise", "nan"):
             raise ValueError("errors must be 'raise' or 'nan'")
+        if scaled:
+            if not getattr(self.spec, "scaled", False):
+                raise ValueError("predict(scaled=True) needs a "
+                                 "SymbRegScaledMSE evaluator: %s fits no "
+                                 "scaling" % type(self.spec).__name__)
+            individuals = list(individuals)
+            # the coefficients of the training cases (an individual with an
+            # erroring training case has none: its exception is raised)
+            for res in self.evaluate(individuals):
+                if isinstance(res, BaseException):
+                    raise res
+            a, b = self.last_scaling
+            vals = self.predict(individuals, X=X, errors=errors,
+                                max_bytes=max_bytes)
+            with np.errstate(invalid="ignore"):     # (0 * inf of a flagged one)
+                return a[:, None] + b[:, None] * vals
         if self.spec.mode == _lib.GPE_MODE_SSE_NUMPY:
             raise NotImplementedError("predict: numpy-semantics specs are not "
                                       "supported")

@@ -60,12 +60,15 @@ typedef struct gpe_ctx gpe_ctx;
 #define GPE_FLAG_NONFINITE_TERM 1u         /* some d was inf or nan        */
 #define GPE_FLAG_NAN_TERM 2u               /* some d*d was nan             */
 #define GPE_FLAG_INF_TERM 4u               /* some d*d was +inf            */
+#define GPE_FLAG_MOMENT_RANGE 8u           /* moments run: some value was
+                                              inf, nan or >= 2^500 in size */
 
 #define GPE_E_INVALID -1
 #define GPE_E_HIP -2
 #define GPE_E_STATE -3
 #define GPE_E_DEPTH -4
 #define GPE_E_COMM -5       /* a collective did not complete within GPE_COMM_TIMEOUT_S */
+#define GPE_E_ARG -6        /* the context's cases / precision do not fit the call */
 
 /* Replaces: the per-process setup of the reference's evaluation
  * (nothing to bind on CPU; the device context owns streams/buffers). */
@@ -162,6 +165,51 @@ int gpe_run_values_device(gpe_ctx* ctx, void* d_values, void* d_err);
  * (multiplexer.py / parity.py evaluate, before the comparison with the
  * outputs). */
 int gpe_run_values_bits(gpe_ctx* ctx, uint32_t* out_planes);
+
+/* A moments run: each loaded program's Sf = sum f, Sff = sum f^2 and
+ * Sfy = sum f y over the resident cases, f the program's value (as
+ * gpe_run_values gives it) and y the cases' one target column.  out6 is a
+ * HOST array double[n_prog][6] = (Sf hi, lo, Sff hi, lo, Sfy hi, lo), each sum
+ * a double-double, summed in a fixed order (the same bits from run to run).
+ * first_err / flags (may be NULL): the first erroring case per program as
+ * gpe_run_values gives it, and GPE_FLAG_MOMENT_RANGE for a program with a
+ * non-finite value or one of magnitude 2^500 or more (such cases are left out
+ * of its sums).  Programs the exact cores hold (at most 12 stack slots and 32
+ * variables, no exact-int pass) run on those cores' moments kernels, which
+ * keep the three sums in LDS; a program with an inf / nan / huge sin/cos
+ * argument in some tile, and every other program, takes the rows route: a
+ * values run into a device scratch of bounded size (16 GiB at most;
+ * GPE_MOMENTS_MB in the environment at gpe_create) reduced there
+ * (moments_rows), in chunks of programs whose rows fit it, one program at
+ * least, so any number of programs and cases is taken.  fp64 on the F machine with exactly one target column,
+ * else GPE_E_ARG.  The resident fitness is not disturbed.
+ * Replaces: three numpy sums over gpe_run_values' n_prog * n_cases matrix. */
+int gpe_run_moments(gpe_ctx* ctx, double* out6, uint64_t* first_err, uint32_t* flags);
+
+/* Linear-scaling fitness (Keijzer 2003) of the loaded programs: the mean
+ * squared error of the best affine fit a + b f to the target, from one
+ * moments run.  sy, syy: the target's sum y and sum y^2 as (hi, lo), computed
+ * exactly by the caller.  With vf = Sff - Sf^2 / n, vy = Syy - Sy^2 / n,
+ * cfy = Sfy - Sf Sy / n:  b = cfy / vf, a = (Sy - b Sf) / n,
+ * mse = (vy - cfy^2 / vf) / n, evaluated in double-double.  Two rules: a
+ * program under GPE_FLAG_MOMENT_RANGE has mse = inf, b = 0, a = Sy / n; one
+ * with n vf <= 2^-40 Sff counts as constant: b = 0, a = Sy / n, mse = vy / n.
+ * HOST arrays of n_prog entries (first_err, flags may be NULL).  Arguments as
+ * gpe_run_moments.
+ * Replaces: predict() and a per-individual numpy regression. */
+int gpe_run_scaled(gpe_ctx* ctx, const double sy[2], const double syy[2], double* mse,
+                   double* a, double* b, uint64_t* first_err, uint32_t* flags);
+
+/* Same, writing DEVICE arrays (d_err, d_flags may be NULL). */
+int gpe_run_scaled_device(gpe_ctx* ctx, const double sy[2], const double syy[2],
+                          void* d_mse, void* d_a, void* d_b, void* d_err, void* d_flags);
+
+/* Host twin of the formula gpe_run_scaled applies on the device (one
+ * function compiled for both): m6 double[n][6], flags uint32[n] (may be
+ * NULL: no flag), outputs double[n]. */
+int gpe_host_scaled_from_moments(const double* m6, int64_t n, int64_t n_cases,
+                                 const double sy[2], const double syy[2],
+                                 const uint32_t* flags, double* mse, double* a, double* b);
 
 /* Device lexicase selection that replays the reference's random stream:
  * selLexicase (mode 0), selEpsilonLexicase (mode 1, epsilon) and
@@ -423,6 +471,9 @@ int gpe_last_geometry_ex(const gpe_ctx* ctx, int64_t* out, int n);
 #define GPE_LAUNCH_CPP_DEEP 4
 #define GPE_LAUNCH_FASM 5
 #define GPE_LAUNCH_DASM 6
+#define GPE_LAUNCH_MOMENTS 7      /* the last moments run's launch of the exact
+                                     D = 5 core's moments kernel ... */
+#define GPE_LAUNCH_MOMENTS_DEEP 8 /* ... and of the exact deep core's */
 #define GPE_LAUNCH_SHAPE_FIELDS 13
 int gpe_last_launch_shape(const gpe_ctx* ctx, int which, int64_t* out, int n);
 
