@@ -2854,7 +2854,12 @@ class Gen(object):
             shared = fam in ("div", "rdiv", "ndiv", "nrdiv")   # long bodies
             for v in range(NV):
                 self.handler("%s_V%d" % (fam, v))
-                self.ldx(self.O(0), v)
+                # experiment "mul_v29_col28" (wrong values, the read stays in
+                # the tile): the exact deep core's mul_V29 alone reads column
+                # 28 — the handler matrix's sensitivity run
+                wrong = os.environ.get("GEN_ASM_EXPERIMENT") == "mul_v29_col28" \
+                    and self.exact and D == 12 and fam == "mul" and v == 29
+                self.ldx(self.O(0), 28 if wrong else v)
                 self.dispatch_head()
                 if shared:
                     self.e("s_branch .Lbody_%s_V_%%=" % fam)
