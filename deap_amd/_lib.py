@@ -57,6 +57,9 @@ SIGNATURES = {
     "gpe_run_scaled_device": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "gpe_host_scaled_from_moments": (_I, [_P, _I64, _I64, _P, _P, _P, _P, _P,
                                           _P]),
+    "gpe_run_abserr": (_I, [_P, ctypes.c_double, _P, _P, _P]),
+    "gpe_run_abserr_device": (_I, [_P, ctypes.c_double, _P, _P, _P]),
+    "gpe_host_abserr": (_I, [_P, _P, _I64, _I64, ctypes.c_double, _P, _P]),
     "gpe_lexicase": (_I, [_P, _P, _I64, _I64, _P, _I, ctypes.c_double, _P,
                           _I64, _P, ctypes.POINTER(_I64)]),
     "gpe_set_lowering": (_I, [_P, _I, _I, _P, _I, _P, _I]),
@@ -203,6 +206,23 @@ def host_scaled_from_moments(m6, n_cases, sy, syy, flags=None):
     if rc != 0:
         raise GpeError("gpe_host_scaled_from_moments failed (%d)" % rc)
     return mse, a, b
+
+
+def host_abserr(f, terms, hit_eps):
+    """Host twin of the abs-error rows reduction (CPU, no GPU): one program's
+    per-case values ``f[n]`` against ``terms[n_terms, n]`` →
+    ``(out4 float64[4] = (sum hi, sum lo, max, hits), flags)``."""
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    t = np.ascontiguousarray(np.atleast_2d(terms), dtype=np.float64)
+    if f.ndim != 1 or t.shape[1] != len(f):
+        raise ValueError("f is [n] and terms [n_terms, n]")
+    out4 = np.zeros(4, dtype=np.float64)
+    flags = np.zeros(1, dtype=np.uint32)
+    rc = load().gpe_host_abserr(_ptr(f), _ptr(t), t.shape[0], len(f),
+                                float(hit_eps), _ptr(out4), _ptr(flags))
+    if rc != 0:
+        raise GpeError("gpe_host_abserr failed (%d)" % rc)
+    return out4, int(flags[0])
 
 
 TRIG_CLASSES = ("general", "mid", "small")
@@ -633,6 +653,29 @@ class Context(object):
                 for p in (mse_ptr, a_ptr, b_ptr, err_ptr, flags_ptr)]),
             "gpe_run_scaled_device")
 
+    def run_abserr(self, hit_eps):
+        """gpe_run_abserr → (out4 float64 [n_prog, 4] = (sum |d| hi, lo,
+        max |d|, hits), err uint64 [n_prog], flags uint32 [n_prog])."""
+        n = self.n_prog
+        out4 = np.zeros((n, 4), dtype=np.float64)
+        err = np.full(n, GPE_NO_ERROR, dtype=np.uint64)
+        flags = np.zeros(n, dtype=np.uint32)
+        if n:
+            self._check(self.lib.gpe_run_abserr(
+                self.h, float(hit_eps), _ptr(out4), _ptr(err), _ptr(flags)),
+                "gpe_run_abserr")
+        return out4, err, flags
+
+    def run_abserr_device(self, hit_eps, out4_ptr, err_ptr=None,
+                          flags_ptr=None):
+        """gpe_run_abserr_device: the results at device addresses (torch
+        tensors' ``data_ptr()``)."""
+        self._check(self.lib.gpe_run_abserr_device(
+            self.h, float(hit_eps), *[
+                ctypes.c_void_p(int(p)) if p else None
+                for p in (out4_ptr, err_ptr, flags_ptr)]),
+            "gpe_run_abserr_device")
+
     def run_values_bits(self):
         """gpe_run_values_bits → uint32 [n_prog, ceil(n_cases / 32)]: the B
         machine's result planes (pad bits 0)."""
@@ -885,7 +928,8 @@ class Context(object):
                         list(g)))
 
     LAUNCHES = ("asm_fast", "asm_deep", "typed", "cpp_fast", "cpp_deep",
-                "fasm", "dasm", "moments", "moments_deep")
+                "fasm", "dasm", "moments", "moments_deep", "abserr",
+                "abserr_deep")
 
     def trig_classes(self, picked=False):
         """sin/cos words of the last exact-core translation per base class

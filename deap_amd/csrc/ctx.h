@@ -448,6 +448,18 @@ struct gpe_ctx {
   double* d_scaled = nullptr;
   size_t scaled_cap = 0;
   int64_t moments_asm = 0, moments_rows = 0;   // programs of the last run per route
+  // An abs-error run (gpe_run_abserr*): the moments run's two routes with the
+  // abs-error kernels (their own copies of the exact cores: jump_a, launch
+  // plans aasm, aasm_deep; two accumulator pairs per program and lane) and
+  // abserr_rows as the rows route's reducer.  d_abs: per program the four
+  // words (sum |d| hi, lo, max |d|, hits); first errors and flags in
+  // d_mom_err / d_mom_flags.
+  std::vector<uint32_t> jump_a[2];
+  uint32_t* d_jump_a[2] = {};
+  Launch aasm, aasm_deep;
+  double hit_eps = 0.0;
+  double* d_abs = nullptr;
+  size_t abs_cap = 0;
   char* h_pin_vals = nullptr;        // pinned staging of gpe_run_values' copy back
   size_t h_pin_vals_cap = 0;
   float ms[3] = {0, 0, 0};

@@ -176,9 +176,18 @@ int run_exact_asm(gpe_ctx* ctx, const std::vector<int32_t>& rx, double* hi,
 // atomics into err / flags (cleared by the caller).  A program with a
 // (program, tile) the core leaves (an inf / nan / huge sin/cos argument) is
 // appended to `rest` whole: its sums here are incomplete.
+// epi = kEpiAbsErr: the abs-error kernels instead (jump_a, aasm / aasm_deep,
+// two accumulator pairs, reduce_groups_abserr into out[n_prog][4], the
+// GPE_FLAG_*_TERM bits into flags).
 int run_moments_asm(gpe_ctx* ctx, const std::vector<int32_t>& rx,
                     const std::vector<int32_t>& rxd, double* out6, unsigned long long* err,
-                    uint32_t* flags, std::vector<int32_t>& rest) {
+                    uint32_t* flags, std::vector<int32_t>& rest, int epi = kEpiMoments) {
+  const bool abs_run = epi == kEpiAbsErr;
+  uint32_t* const* const d_jump = abs_run ? ctx->d_jump_a : ctx->d_jump_m;
+  Launch& L5 = abs_run ? ctx->aasm : ctx->masm;
+  Launch& Ld = abs_run ? ctx->aasm_deep : ctx->masm_deep;
+  const int accw = abs_run ? 2 : 3;
+  auto reduce = abs_run ? launch_reduce_abserr : launch_reduce_moments;
   const int64_t n_prog = ctx->n_prog;
   std::vector<uint8_t> cls((size_t)n_prog, 0);
   for (const std::vector<int32_t>* v : {&rx, &rxd})
@@ -188,9 +197,9 @@ int run_moments_asm(gpe_ctx* ctx, const std::vector<int32_t>& rx,
   for (int32_t i : rx) cls[(size_t)i] = 1;
   for (int32_t i : rxd) cls[(size_t)i] = 2;
   XlateTabs T{};
-  T.tab[0] = T.tab[2] = ctx->d_jump_m[0];
+  T.tab[0] = T.tab[2] = d_jump[0];
   T.ids[0] = T.ids[2] = kIds;
-  T.tab[1] = ctx->d_jump_m[1];
+  T.tab[1] = d_jump[1];
   T.ids[1] = kIdsExactDeep;
   if (int rc0 = translate_device(ctx, &cls, T, false, false, &ctx->d_acode_x, &ctx->acode_x_cap,
                                  &ctx->d_astart_x, &ctx->astart_x_cap, true))
@@ -200,14 +209,14 @@ int run_moments_asm(gpe_ctx* ctx, const std::vector<int32_t>& rx,
   HIPCHK(hipMemsetAsync(ctx->d_redo2_count, 0, sizeof(uint32_t), ctx->stream));
   const int64_t keep = ctx->asm_target_blocks;
   ctx->asm_target_blocks = ctx->xasm_target_blocks;
-  int rc = plan(ctx, ctx->masm, rx, false, true, false, false, true, 3);
+  int rc = plan(ctx, L5, rx, false, true, false, false, true, accw);
   ctx->asm_target_blocks = keep;
   if (rc) return rc;
-  if ((rc = plan(ctx, ctx->masm_deep, rxd, false, true, true, false, true, 3))) return rc;
-  if ((rc = launch_asm(ctx, ctx->masm, err, flags, false, true, true))) return rc;
-  if ((rc = launch_asm(ctx, ctx->masm_deep, err, flags, true, true, true))) return rc;
-  if ((rc = launch_reduce_moments(ctx, ctx->masm, out6))) return rc;
-  if ((rc = launch_reduce_moments(ctx, ctx->masm_deep, out6))) return rc;
+  if ((rc = plan(ctx, Ld, rxd, false, true, true, false, true, accw))) return rc;
+  if ((rc = launch_asm(ctx, L5, err, flags, false, true, epi))) return rc;
+  if ((rc = launch_asm(ctx, Ld, err, flags, true, true, epi))) return rc;
+  if ((rc = reduce(ctx, L5, out6))) return rc;
+  if ((rc = reduce(ctx, Ld, out6))) return rc;
   uint32_t cnt = 0;
   HIPCHK(hipMemcpyAsync(&cnt, ctx->d_redo2_count, sizeof(uint32_t), hipMemcpyDeviceToHost,
                         ctx->stream));

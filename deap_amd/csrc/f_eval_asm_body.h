@@ -1,6 +1,6 @@
-// The body of f_eval_asm, f_eval_asm_values and f_eval_asm_moments
-// (asm_kernels.h includes this file inside each of the three kernel templates,
-// after `constexpr int EPILOGUE`): one text, three kernels.  The fitness kernel is compiled from exactly the
+// The body of f_eval_asm, f_eval_asm_values, f_eval_asm_moments and
+// f_eval_asm_abserr (asm_kernels.h includes this file inside each of the four
+// kernel templates, after `constexpr int EPILOGUE`): one text, four kernels.  The fitness kernel is compiled from exactly the
 // text it always had (its VALUES branch is discarded), so its registers do not
 // depend on the values epilogue; each kernel holds its own copy of its core
 // and has its own jump table (init_asm).
@@ -9,8 +9,10 @@
 // slots.  Same geometry, staging, epilogue and redo.
   [[maybe_unused]] constexpr bool VALUES = EPILOGUE == kEpiValues;
   [[maybe_unused]] constexpr bool MOMENTS = EPILOGUE == kEpiMoments;
-  // accumulator pairs per program and lane (moments: f, f f, f y)
-  constexpr int ACCW = MOMENTS ? 3 : 1;
+  [[maybe_unused]] constexpr bool ABSERR = EPILOGUE == kEpiAbsErr;
+  // accumulator pairs per program and lane (moments: f, f f, f y; abs error:
+  // the sum of |d|, then (max |d|, hits))
+  constexpr int ACCW = MOMENTS ? 3 : ABSERR ? 2 : 1;
   using R = typename std::conditional<F32, float, double>::type;
   // cases per lane of this kernel's core (the D = 5 fast core may hold more
   // than the deep and exact cores)
@@ -82,8 +84,8 @@
   uint32_t done_mask = 0;      // fp64: this wave's programs already flagged
   // fp64 MSE with one target column and no per-case output: the lean
   // epilogue (below) on full tiles
-  // (a moments run: the core returns at END for every program)
-  const bool lean = !MOMENTS && !F32 && a.nt == 1 && a.case_out == nullptr;
+  // (a moments or abs-error run: the core returns at END for every program)
+  const bool lean = !MOMENTS && !ABSERR && !F32 && a.nt == 1 && a.case_out == nullptr;
   Task st{};
   st.X = a.X;
   st.nv = a.nv;
@@ -256,6 +258,36 @@
         }
         return;
       }
+      if constexpr (ABSERR) {
+        // an abs-error run (f_eval_asm_abserr): per valid case d, formed as the
+        // general path below forms it, into the lane's four words of program j
+        // (abserr::accumulate: sum |d|, max |d|, hits); pad lanes add nothing
+        double* const ac = acc + (size_t)(4 * j) * 64 + lane;
+        abserr::Part p{ac[0], ac[64], ac[128], ac[192]};
+        unsigned long long verr_at = ~0ull;
+        uint32_t flag = 0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const int64_t c = case0 + k * 64;
+          if (c < a.n_cases) {
+            double dlt = (double)T[k];
+            for (int q = 0; q < a.nt; ++q) dlt = dlt - (double)ts[(q * K + k) * 64 + lane];
+            if ((vbits >> k) & 1u)
+              verr_at = min(verr_at, ((unsigned long long)c << 2) | GPE_ERR_VALUE);
+            abserr::accumulate(p, flag, dlt, a.hit_eps);
+          }
+        }
+        ac[0] = p.hi;
+        ac[64] = p.lo;
+        ac[128] = p.mx;
+        ac[192] = p.hits;
+        if (verr_at != ~0ull) atomicMin(&a.first_err[prog], verr_at);
+        if (__builtin_amdgcn_ballot_w64(flag != 0)) {
+          for (int m = 32; m >= 1; m >>= 1) flag |= __shfl_xor(flag, m, 64);
+          if (lane == 0) atomicOr(&a.flags[prog], flag);
+        }
+        return;
+      }
       double hi = acc[(2 * j) * 64 + lane], lo = acc[(2 * j + 1) * 64 + lane];
       if (lean && full) {
         // the common case: one target column, every case of the tile valid,
@@ -425,14 +457,20 @@
     }
   }
   // one cross-lane reduction per program per tile group (moments: of each
-  // of the three pairs, six words per slot)
+  // of the three pairs, six words per slot; abs error: the sum's pair, then
+  // the (max, hits) pair by max and add, four words per slot)
 #pragma nounroll
   for (int j = 0; j < n_mine * ACCW; ++j) {
     double hi = acc[(2 * j) * 64 + lane], lo = acc[(2 * j + 1) * 64 + lane];
     for (int m = 32; m >= 1; m >>= 1) {
       const double ohi = shfl_xor_d(hi, m);
       const double olo = shfl_xor_d(lo, m);
-      dd_add(hi, lo, ohi, olo);
+      if (ABSERR && (j & 1)) {
+        if (ohi > hi) hi = ohi;
+        lo += olo;
+      } else {
+        dd_add(hi, lo, ohi, olo);
+      }
     }
     if (lane == 0) {
       double* p = a.part + ((size_t)grp * a.n_slots * ACCW + slot0 * ACCW + j) * 2;

@@ -54,6 +54,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <functional>
 #include <vector>
 
 #include "../../include/gpeval.h"
@@ -178,6 +179,7 @@ __device__ __forceinline__ double shfl_xor_d(double v, int m) {
 }  // namespace
 #include "trig_dev.h"
 #include "exact_int.h"
+#include "abserr.h"
 #include "fb_kernels.h"
 #include "asm_kernels.h"
 #include "rccl_layer.h"
@@ -1236,6 +1238,10 @@ int init_asm(gpe_ctx* ctx) {
                   ctx->asm_exact_table, ctx->jump_m[0], "moments exact asm")) ||
       (rc = jumps(eval_probe(f_eval_asm_moments<false, true, true>, true, false),
                   ctx->asm_exact_deep_table, ctx->jump_m[1], "moments exact deep asm")) ||
+      (rc = jumps(eval_probe(f_eval_asm_abserr<false, false, true>, true, false),
+                  ctx->asm_exact_table, ctx->jump_a[0], "abs-error exact asm")) ||
+      (rc = jumps(eval_probe(f_eval_asm_abserr<false, true, true>, true, false),
+                  ctx->asm_exact_deep_table, ctx->jump_a[1], "abs-error exact deep asm")) ||
       (rc = jumps([&](uint32_t* d) {
                     constexpr int K = asmcore_typed::K;
                     AsmTask t{};
@@ -1302,7 +1308,8 @@ int init_asm(gpe_ctx* ctx) {
   for (int k = 0; k < kJvCount; ++k)
     if (upload(ctx->jump_v[k], &ctx->d_jump_v[k])) return GPE_E_HIP;
   for (int k = 0; k < 2; ++k)
-    if (upload(ctx->jump_m[k], &ctx->d_jump_m[k])) return GPE_E_HIP;
+    if (upload(ctx->jump_m[k], &ctx->d_jump_m[k]) || upload(ctx->jump_a[k], &ctx->d_jump_a[k]))
+      return GPE_E_HIP;
   ctx->asm_ready = true;
   return 0;
 }
@@ -1810,7 +1817,9 @@ void gpe_destroy(gpe_ctx* ctx) {
                   ctx->d_mom_err, ctx->d_mom_flags, ctx->d_scaled, ctx->d_mom_err2,
                   ctx->d_mlist, ctx->d_jump_m[0], ctx->d_jump_m[1],
                   ctx->masm.d_slot_prog, ctx->masm.d_part, ctx->masm_deep.d_slot_prog,
-                  ctx->masm_deep.d_part};
+                  ctx->masm_deep.d_part, ctx->d_jump_a[0], ctx->d_jump_a[1], ctx->d_abs,
+                  ctx->aasm.d_slot_prog, ctx->aasm.d_part, ctx->aasm_deep.d_slot_prog,
+                  ctx->aasm_deep.d_part};
   if (ctx->comm && rccl().ok) (void)rccl().comm_destroy(ctx->comm);
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -1832,7 +1841,7 @@ void gpe_destroy(gpe_ctx* ctx) {
   if (ctx->lw_hm) (void)hipHostFree(ctx->lw_hm);
   for (Launch* L : {&ctx->fast, &ctx->deep, &ctx->fasm, &ctx->dasm, &ctx->tasm, &ctx->redo_fast,
                     &ctx->redo_deep, &ctx->redo_xasm, &ctx->redo_xasm_deep, &ctx->masm,
-                    &ctx->masm_deep})
+                    &ctx->masm_deep, &ctx->aasm, &ctx->aasm_deep})
     if (L->h_pin) (void)hipHostFree(L->h_pin);
   for (auto& e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
@@ -2794,9 +2803,16 @@ int moments_check(gpe_ctx* ctx) {
 // whose rows fit ctx->moments_bytes, a values run of the listed programs of
 // that range alone (plan_mode's sub_lo / sub_hi / sub_mask), moments_rows on
 // them.  d_err / d_flags: device arrays of n_prog entries.
-int run_moments(gpe_ctx* ctx, unsigned long long* d_err, uint32_t* d_flags) {
+// An abs-error run (run_abserr) takes the same two routes with its own
+// kernels (epi = kEpiAbsErr), results array and reducer: `d_out` is the
+// per-program results array of the run, `reduce(p0, list, m)` the rows
+// route's reducer on a chunk's m listed programs, whose rows start at p0.
+int run_routes(gpe_ctx* ctx, unsigned long long* d_err, uint32_t* d_flags, int epi,
+               double* d_out,
+               const std::function<void(int64_t, const int32_t*, int64_t)>& reduce) {
   const int64_t np = ctx->n_prog, nc = ctx->n_cases;
-  if (ensure(ctx, &ctx->d_mom, &ctx->mom_cap, 6 * (size_t)np)) return GPE_E_HIP;
+  Launch& L5 = epi == kEpiAbsErr ? ctx->aasm : ctx->masm;
+  Launch& Ld = epi == kEpiAbsErr ? ctx->aasm_deep : ctx->masm_deep;
   HIPCHK(hipMemsetAsync(d_err, 0xff, (size_t)np * sizeof(unsigned long long), ctx->stream));
   HIPCHK(hipMemsetAsync(d_flags, 0, (size_t)np * sizeof(uint32_t), ctx->stream));
   // the two routes' programs
@@ -2813,8 +2829,8 @@ int run_moments(gpe_ctx* ctx, unsigned long long* d_err, uint32_t* d_flags) {
       if (c == 1 || c == 2) rows_mask[(size_t)i] = 0;
     }
   }
-  ctx->masm.programs = ctx->masm_deep.programs = 0;
-  ctx->masm.lds = ctx->masm_deep.lds = 0;
+  L5.programs = Ld.programs = 0;
+  L5.lds = Ld.lds = 0;
   if (!rx.empty() || !rxd.empty()) {
     if (ctx->trig_leaves) {          // (the leaf columns, as run_common computes them)
       const int64_t n = nc * ctx->nv_user;
@@ -2822,7 +2838,7 @@ int run_moments(gpe_ctx* ctx, unsigned long long* d_err, uint32_t* d_flags) {
                          ctx->stream, (double*)ctx->d_X, ctx->nv_user, nc, 0);
       HIPCHK(hipGetLastError());
     }
-    if (int rc = run_moments_asm(ctx, rx, rxd, ctx->d_mom, d_err, d_flags, rest)) return rc;
+    if (int rc = run_moments_asm(ctx, rx, rxd, d_out, d_err, d_flags, rest, epi)) return rc;
     for (const int32_t p : rest) rows_mask[(size_t)p] = 1;
   }
   std::vector<int32_t> list;
@@ -2871,11 +2887,48 @@ int run_moments(gpe_ctx* ctx, unsigned long long* d_err, uint32_t* d_flags) {
                        (const int32_t*)ctx->d_mlist + a, m,
                        (const unsigned long long*)ctx->d_mom_err2, d_err);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(moments_rows, dim3((unsigned)m), dim3(256), 0, ctx->stream,
-                       (const double*)ctx->d_mrows, nc, (const double*)ctx->d_terms, p0,
-                       (const int32_t*)ctx->d_mlist + a, ctx->d_mom, d_flags);
+    reduce(p0, (const int32_t*)ctx->d_mlist + a, m);
     HIPCHK(hipGetLastError());
   }
+  return 0;
+}
+
+int run_moments(gpe_ctx* ctx, unsigned long long* d_err, uint32_t* d_flags) {
+  const int64_t nc = ctx->n_cases;
+  if (ensure(ctx, &ctx->d_mom, &ctx->mom_cap, 6 * (size_t)ctx->n_prog)) return GPE_E_HIP;
+  return run_routes(ctx, d_err, d_flags, kEpiMoments, ctx->d_mom,
+                    [&](int64_t p0, const int32_t* list, int64_t m) {
+                      hipLaunchKernelGGL(moments_rows, dim3((unsigned)m), dim3(256), 0,
+                                         ctx->stream, (const double*)ctx->d_mrows, nc,
+                                         (const double*)ctx->d_terms, p0, list, ctx->d_mom,
+                                         d_flags);
+                    });
+}
+
+// The abs-error words of the loaded programs into ctx->d_abs: the moments
+// run's routes (run_routes) with the abs-error kernels and abserr_rows, which
+// subtracts the staged term columns from the chunk's values.
+int run_abserr(gpe_ctx* ctx, double hit_eps, unsigned long long* d_err, uint32_t* d_flags) {
+  const int64_t nc = ctx->n_cases;
+  if (ensure(ctx, &ctx->d_abs, &ctx->abs_cap, 4 * (size_t)ctx->n_prog)) return GPE_E_HIP;
+  ctx->hit_eps = hit_eps;
+  return run_routes(ctx, d_err, d_flags, kEpiAbsErr, ctx->d_abs,
+                    [&](int64_t p0, const int32_t* list, int64_t m) {
+                      hipLaunchKernelGGL(abserr_rows, dim3((unsigned)m), dim3(256), 0,
+                                         ctx->stream, (const double*)ctx->d_mrows, nc,
+                                         (const double*)ctx->d_terms, ctx->nt, hit_eps, p0, list,
+                                         ctx->d_abs, d_flags);
+                    });
+}
+
+int abserr_check(gpe_ctx* ctx, double hit_eps) {
+  if (ctx->machine != GPE_MACHINE_F)
+    return fail(ctx, GPE_E_ARG, "an abs-error run needs the F machine");
+  if (ctx->prec != GPE_PREC_F64)
+    return fail(ctx, GPE_E_ARG, "an abs-error run is fp64 (the context is in fp32 mode)");
+  if (!(hit_eps >= 0.0))
+    return fail(ctx, GPE_E_ARG, "an abs-error run's hit_eps is negative or nan");
+  if (ctx->n_prog <= 0) return fail(ctx, GPE_E_INVALID, "abs-error run: no programs loaded");
   return 0;
 }
 
@@ -2898,6 +2951,47 @@ int moments_side_buffers(gpe_ctx* ctx) {
   return 0;
 }
 }  // namespace
+
+int gpe_run_abserr_device(gpe_ctx* ctx, double hit_eps, void* d_out4, void* d_err,
+                          void* d_flags) {
+  if (!ctx || !d_out4) return GPE_E_INVALID;
+  if (int rc = abserr_check(ctx, hit_eps)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = moments_side_buffers(ctx)) return rc;
+  if (int rc = run_abserr(ctx, hit_eps, d_err ? (unsigned long long*)d_err : ctx->d_mom_err,
+                          d_flags ? (uint32_t*)d_flags : ctx->d_mom_flags))
+    return rc;
+  HIPCHK(hipMemcpyAsync(d_out4, ctx->d_abs, 4 * (size_t)ctx->n_prog * sizeof(double),
+                        hipMemcpyDeviceToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+int gpe_run_abserr(gpe_ctx* ctx, double hit_eps, double* out4, uint64_t* first_err,
+                   uint32_t* flags) {
+  if (!ctx || !out4) return GPE_E_INVALID;
+  if (int rc = abserr_check(ctx, hit_eps)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = moments_side_buffers(ctx)) return rc;
+  if (int rc = run_abserr(ctx, hit_eps, ctx->d_mom_err, ctx->d_mom_flags)) return rc;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const size_t np = (size_t)ctx->n_prog;
+  if (int rc = values_to_host(ctx, out4, ctx->d_abs, 4 * np * sizeof(double))) return rc;
+  if (first_err)
+    if (int rc = values_to_host(ctx, first_err, ctx->d_mom_err, np * sizeof(uint64_t))) return rc;
+  if (flags)
+    if (int rc = values_to_host(ctx, flags, ctx->d_mom_flags, np * sizeof(uint32_t))) return rc;
+  return 0;
+}
+
+int gpe_host_abserr(const double* f, const double* terms, int64_t n_terms, int64_t n_cases,
+                    double hit_eps, double* out4, uint32_t* flags) {
+  if (!f || (n_terms > 0 && !terms) || n_terms < 0 || n_cases <= 0 || !out4)
+    return GPE_E_INVALID;
+  if (!(hit_eps >= 0.0)) return GPE_E_ARG;
+  abserr::host_row(f, terms, n_terms, n_cases, hit_eps, out4, flags);
+  return 0;
+}
 
 int gpe_run_moments(gpe_ctx* ctx, double* out6, uint64_t* first_err, uint32_t* flags) {
   if (!ctx || !out6) return GPE_E_INVALID;
@@ -3891,6 +3985,8 @@ int gpe_last_launch_shape(const gpe_ctx* ctx, int which, int64_t* o, int n) {
     case GPE_LAUNCH_DASM: L = &ctx->dasm; break;
     case GPE_LAUNCH_MOMENTS: L = &ctx->masm; break;
     case GPE_LAUNCH_MOMENTS_DEEP: L = &ctx->masm_deep; break;
+    case GPE_LAUNCH_ABSERR: L = &ctx->aasm; break;
+    case GPE_LAUNCH_ABSERR_DEEP: L = &ctx->aasm_deep; break;
     default: return GPE_E_INVALID;
   }
   const int64_t g[GPE_LAUNCH_SHAPE_FIELDS] = {

@@ -51,7 +51,8 @@ bool asm_dbuf(const gpe_ctx* ctx, int K) {
 }
 
 // accw: accumulator pairs per program and lane (1: the fitness and values
-// kernels, 1 KiB per program per wave; 3: the moments kernels, 3 KiB)
+// kernels, 1 KiB per program per wave; 3: the moments kernels, 3 KiB; 2: the
+// abs-error kernels, 2 KiB)
 size_t lds_bytes_asm(const gpe_ctx* ctx, int P, int wpb, int K, bool dbuf,
                      bool exact = false, int accw = 1) {
   const bool f32 = !exact && ctx->prec == GPE_PREC_F32 && K == asmcore32::K;
@@ -353,7 +354,10 @@ int launch_f(gpe_ctx* ctx, Launch& L, bool deep, unsigned long long* err,
 
 int launch_asm(gpe_ctx* ctx, Launch& L, unsigned long long* err,
                uint32_t* flags, bool deep_core = false, bool exact = false,
-               bool moments = false) {
+               int epi = kEpiFitness) {
+  // (epi: kEpiMoments / kEpiAbsErr pick those runs' kernels; a values run is
+  // ctx->values_on)
+  const bool moments = epi == kEpiMoments, abserr = epi == kEpiAbsErr;
   if (L.n_slots == 0) return 0;
   AsmTask a{};
   a.code = exact ? ctx->d_acode_x : ctx->d_acode;
@@ -388,13 +392,15 @@ int launch_asm(gpe_ctx* ctx, Launch& L, unsigned long long* err,
     a.cst = ctx->d_cst_exact;
   }
   a.dbuf = L.dbuf ? 1 : 0;
+  a.hit_eps = ctx->hit_eps;
   // the resident tile loop: f_eval_asm's conditions (its kResident core on a
   // lean, double-buffered launch)
   L.resident = exact && !deep_core && GP_ASM_LOOP_EXACT && GP_ASM_TILE_LOOP_EXACT &&
                ctx->tile_loop && L.dbuf && L.K * 64 * sizeof(double) == 1024 &&
-               a.nt == 1 && a.case_out == nullptr && a.n_tiles < (1ll << 31) && !moments;
+               a.nt == 1 && a.case_out == nullptr && a.n_tiles < (1ll << 31) && !moments &&
+               !abserr;
   a.tile_loop = L.resident ? 1 : 0;
-  const size_t lds = lds_bytes_asm(ctx, L.P, L.wpb, L.K, L.dbuf, exact, moments ? 3 : 1);
+  const size_t lds = lds_bytes_asm(ctx, L.P, L.wpb, L.K, L.dbuf, exact, moments ? 3 : abserr ? 2 : 1);
   L.lds = lds;
   const bool f32 = ctx->prec == GPE_PREC_F32;
   auto kern = exact ? (deep_core ? f_eval_asm<false, true, true> : f_eval_asm<false, false, true>)
@@ -411,6 +417,12 @@ int launch_asm(gpe_ctx* ctx, Launch& L, unsigned long long* err,
       return fail(ctx, GPE_E_STATE, "moments kernels: exact fp64 cores, one target column");
     kern = deep_core ? f_eval_asm_moments<false, true, true>
                      : f_eval_asm_moments<false, false, true>;
+  }
+  if (abserr) {                // the exact cores' abs-error kernels (jump_a)
+    if (!exact || f32 || ctx->values_on)
+      return fail(ctx, GPE_E_STATE, "abs-error kernels: exact fp64 cores");
+    kern = deep_core ? f_eval_asm_abserr<false, true, true>
+                     : f_eval_asm_abserr<false, false, true>;
   }
   HIPCHK(hipFuncSetAttribute((const void*)kern,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -502,6 +514,16 @@ int launch_reduce_moments(gpe_ctx* ctx, Launch& L, double* out6) {
   const unsigned blocks = (unsigned)((L.n_slots + 255) / 256);
   hipLaunchKernelGGL(reduce_groups_moments, dim3(blocks), dim3(256), 0, ctx->stream,
                      L.d_part, L.n_slots, L.groups, L.d_slot_prog, out6);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// the abs-error kernels' four words per slot and tile group into [n_prog][4]
+int launch_reduce_abserr(gpe_ctx* ctx, Launch& L, double* out4) {
+  if (L.n_slots == 0) return 0;
+  const unsigned blocks = (unsigned)((L.n_slots + 255) / 256);
+  hipLaunchKernelGGL(reduce_groups_abserr, dim3(blocks), dim3(256), 0, ctx->stream,
+                     L.d_part, L.n_slots, L.groups, L.d_slot_prog, out4);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -120,6 +120,11 @@ def _check_shardable(spec, case_sharded):
         raise NotImplementedError("SymbRegScaledMSE runs on one GPU: the "
                                   "moments are additive over case shards, "
                                   "but no sharded moments run is built")
+    if getattr(spec, "abs_error", False):
+        raise NotImplementedError("SymbRegAbsError runs on one GPU: the sum, "
+                                  "the max and the hits combine over case "
+                                  "shards, but no sharded abs-error run is "
+                                  "built")
     if getattr(spec, "per_case", False):
         raise NotImplementedError("per-case outputs are not gathered across "
                                   "ranks; evaluate per-case specs on one GPU")

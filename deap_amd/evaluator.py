@@ -46,7 +46,8 @@ def _tuples1(values, as_int):
 
 
 __all__ = ["SymbRegMSE", "SymbRegNumpySSE", "SymbRegSumSSE",
-           "SymbRegScaledMSE", "SymbRegCaseErrors", "BooleanHits",
+           "SymbRegScaledMSE", "SymbRegAbsError", "SymbRegCaseErrors",
+           "BooleanHits",
            "exact_dd_sums",
            "TypedBoolHits", "GPUEvaluator", "gpu_map", "pack_bitplanes",
            "unpack_bitplanes", "plan_predict_chunks", "first_error_cases",
@@ -250,24 +251,111 @@ class SymbRegScaledMSE(SymbRegMSE):
         return out
 
 
+class SymbRegAbsError(SymbRegMSE):
+    """Absolute-error fitness from one GPU pass (``gpe_run_abserr``).  With
+    ``e_i = abs(f(*row_i) - t0_i - t1_i - ...)`` (the terms subtracted left to
+    right, as :class:`SymbRegMSE` without the square):
+
+    * ``"mae"``: ``math.fsum(e) / n``;
+    * ``"max"``: ``float(numpy.max(e))`` — nan if any ``e_i`` is nan, else the
+      largest (inf included);
+    * ``"hits"``: Koza's hits, ``sum(1 for v in e if v <= hit_eps)`` as an
+      ``int``; a nan or inf ``e_i`` is never a hit, also with
+      ``hit_eps = inf``.
+
+    *fitness* is a non-empty tuple drawn from those names: the fitness tuple's
+    entries, in that order.  A case whose call raises (``math.sin(inf)``,
+    ``math.sqrt(-1)``, ``float(int)`` overflow) raises for that individual, as
+    in :class:`SymbRegMSE`; there is no ``d**2``, so no ``OverflowError`` from
+    a large difference.  ``fsum`` as :meth:`SymbRegMSE.finish` states it: all
+    ``e_i`` finite and the sum overflows: ``OverflowError("intermediate
+    overflow in fsum")`` (whatever *fitness* names: the reference computes
+    all three); some ``e_i`` inf and none nan: ``mae = inf``; some nan:
+    ``mae = nan``.  After an evaluation ``GPUEvaluator.last_mae``,
+    ``last_max_error`` (float64) and ``last_hits`` (int64) hold all three per
+    individual (nan / -1 for one that raised).
+
+    fp64, Python-semantics untyped primitive sets, one GPU."""
+    abs_error = True
+    NAMES = ("mae", "max", "hits")
+
+    def __init__(self, X, terms, hit_eps=0.01, fitness=("mae",)):
+        SymbRegMSE.__init__(self, X, terms)
+        hit_eps = float(hit_eps)
+        if not hit_eps >= 0.0:
+            raise ValueError("hit_eps must be >= 0 (got %r)" % hit_eps)
+        if isinstance(fitness, str):
+            fitness = (fitness,)
+        fitness = tuple(fitness)
+        if not fitness or any(k not in self.NAMES for k in fitness):
+            raise ValueError("fitness must be a non-empty tuple drawn from "
+                             "%r (got %r)" % (self.NAMES, fitness))
+        self.hit_eps = hit_eps
+        self.fitness = fitness
+
+    def figures(self, w4, err, flags):
+        """``(mae, max, hits)`` arrays (float64, float64, int64) of a batch's
+        abs-error words ``[n, 4]``; nan / -1 where the individual raises (a
+        first error, or an fsum overflow)."""
+        w4 = np.asarray(w4, dtype=np.float64).reshape(-1, 4)
+        flags = np.asarray(flags)
+        nan_t = (flags & _lib.GPE_FLAG_NAN_TERM) != 0
+        inf_t = ((flags & _lib.GPE_FLAG_INF_TERM) != 0) & ~nan_t
+        with np.errstate(all="ignore"):
+            mae = w4[:, 0] / self.n_cases
+        mx = w4[:, 2].copy()
+        mae[inf_t] = mx[inf_t] = math.inf
+        mae[nan_t] = mx[nan_t] = math.nan
+        hits = w4[:, 3].astype(np.int64)
+        raised = (np.asarray(err) != np.uint64(_lib.GPE_NO_ERROR)) | (
+            ~np.isfinite(w4[:, 0]) & ~nan_t & ~inf_t)
+        mae[raised] = mx[raised] = math.nan
+        hits[raised] = -1
+        return mae, mx, hits
+
+    def finish(self, i, w4, lo, err, flags):
+        if err != _lib.GPE_NO_ERROR:
+            return _case_error(err)
+        mae, mx, hits = self.figures(w4, [err], [flags])
+        if hits[0] < 0:
+            return OverflowError("intermediate overflow in fsum")
+        vals = {"mae": float(mae[0]), "max": float(mx[0]), "hits": int(hits[0])}
+        return tuple(vals[k] for k in self.fitness)
+
+    def finish_all(self, w4, lo, err, flags):
+        mae, mx, hits = self.figures(w4, err, flags)
+        cols = {"mae": mae.tolist(), "max": mx.tolist(), "hits": hits.tolist()}
+        out = list(zip(*[cols[k] for k in self.fitness]))
+        for i in np.flatnonzero(hits < 0).tolist():
+            out[i] = self.finish(i, w4[i], None, err[i], flags[i])
+        return out
+
+
 def _check_scaled_setup(spec, pset, flattener, precision):
-    """A linear-scaling spec's evaluator: what it refuses, and why."""
+    """A moments-route spec's evaluator (linear scaling, absolute error): what
+    it refuses, and why."""
+    name = type(spec).__name__
     if precision == "fp32":
-        raise ValueError("SymbRegScaledMSE is fp64 only: a one-pass variance "
-                         "has no digits to spare in precision='fp32'")
+        raise ValueError(
+            "%s is fp64 only: %s" % (name, "a one-pass variance has no digits "
+                                     "to spare in precision='fp32'"
+                                     if getattr(spec, "scaled", False) else
+                                     "its kernels are the exact fp64 cores' "
+                                     "(no precision='fp32')"))
     sems = set(flattener.spec.prim_ops.values())
     np_sems = sorted(s for s in sems if s.startswith("np"))
     if np_sems:
         raise NotImplementedError(
-            "SymbRegScaledMSE needs Python-semantics primitives; this set has "
+            "%s needs Python-semantics primitives; this set has "
             "numpy-semantics ones (%s), whose sin/cos(inf) and division are "
-            "values, not errors" % ", ".join(np_sems))
+            "values, not errors" % (name, ", ".join(np_sems)))
     for p in (pset if isinstance(pset, (list, tuple)) else [pset]):
         if getattr(p, "ret", object) is not object:
             raise NotImplementedError(
-                "SymbRegScaledMSE does not take a typed primitive set (%s "
-                "returns %r): the moments run covers float programs only"
-                % (getattr(p, "name", "pset"), p.ret))
+                "%s does not take a typed primitive set (%s "
+                "returns %r): the %s run covers float programs only"
+                % (name, getattr(p, "name", "pset"), p.ret,
+                   "moments" if getattr(spec, "scaled", False) else "abs-error"))
 
 
 class SymbRegCaseErrors(SymbRegMSE):
@@ -470,7 +558,7 @@ class GPUEvaluator(object):
         if self.flattener.machine != spec.machine:
             raise ValueError("fitness spec and primitive set need different "
                              "machines")
-        if getattr(spec, "scaled", False):
+        if getattr(spec, "scaled", False) or getattr(spec, "abs_error", False):
             _check_scaled_setup(spec, pset, self.flattener, precision)
         self.ctx = _lib.Context(_default_device() if device is None
                                 else device)
@@ -514,6 +602,10 @@ class GPUEvaluator(object):
         self.last_predict_first_error = np.zeros(0, dtype=np.int64)
         # SymbRegScaledMSE: (a, b) float64 [n] of the last evaluation
         self.last_scaling = (np.zeros(0), np.zeros(0))
+        # SymbRegAbsError: all three figures of the last evaluation
+        self.last_mae = np.zeros(0)
+        self.last_max_error = np.zeros(0)
+        self.last_hits = np.zeros(0, dtype=np.int64)
 
     def close(self):
         """Release the device contexts (the evaluator's and predict's)."""
@@ -760,6 +852,12 @@ class GPUEvaluator(object):
                                                        self.spec.syy)
             lo = np.zeros_like(hi)
             self.last_scaling = (a, b)
+        elif getattr(self.spec, "abs_error", False):
+            # (the four words per program in hi's place)
+            hi, err, flags = self.ctx.run_abserr(self.spec.hit_eps)
+            lo = np.zeros(len(err))
+            self.last_mae, self.last_max_error, self.last_hits = \
+                self.spec.figures(hi, err, flags)
         elif getattr(self.spec, "per_case", False):
             cases, hi, lo, err, flags = self.ctx.run_cases(
                 self.spec.mode, self.spec.n_cases)

@@ -211,6 +211,38 @@ int gpe_host_scaled_from_moments(const double* m6, int64_t n, int64_t n_cases,
                                  const double sy[2], const double syy[2],
                                  const uint32_t* flags, double* mse, double* a, double* b);
 
+/* An abs-error run: each loaded program's absolute-error figures over the
+ * resident cases.  With e = |f - t0 - t1 - ...| per case (f the program's
+ * value, the term columns subtracted left to right as the MSE modes do),
+ * out4 is a HOST array double[n_prog][4] = (sum e hi, lo, max e, hits): the
+ * sum a double-double summed in a fixed order (the same bits from run to run),
+ * the max ignoring nan, and hits the number of cases with e <= hit_eps (a
+ * whole number held as a double; a nan or inf e is never a hit, also with
+ * hit_eps = inf).  flags (may be NULL): GPE_FLAG_NAN_TERM for a program with a
+ * nan e (its max and mean are nan by definition; the caller applies that) and
+ * GPE_FLAG_INF_TERM for one with an inf e, each with GPE_FLAG_NONFINITE_TERM.
+ * A sum that is inf with no flag set overflowed from finite terms.  first_err
+ * (may be NULL): the first erroring case per program as gpe_run_values gives
+ * it.  Routes as gpe_run_moments: the exact cores' abs-error kernels keep the
+ * four words in LDS; every other program, and one with a redo tile, takes the
+ * rows route (chunked values runs reduced by abserr_rows; GPE_MOMENTS_MB).
+ * fp64 on the F machine and hit_eps >= 0, else GPE_E_ARG.  The resident
+ * fitness is not disturbed.
+ * Replaces: numpy.abs over gpe_run_values' n_prog * n_cases matrix. */
+int gpe_run_abserr(gpe_ctx* ctx, double hit_eps, double* out4, uint64_t* first_err,
+                   uint32_t* flags);
+
+/* Same, writing DEVICE arrays (d_err, d_flags may be NULL). */
+int gpe_run_abserr_device(gpe_ctx* ctx, double hit_eps, void* d_out4, void* d_err,
+                          void* d_flags);
+
+/* Host twin of the rows route's reduction (no GPU): the four words and the
+ * flags of one row f[n_cases] of per-case values against
+ * terms[n_terms][n_cases], in abserr_rows' order (256 strided partials, the
+ * same fixed tree, the same per-case function). */
+int gpe_host_abserr(const double* f, const double* terms, int64_t n_terms, int64_t n_cases,
+                    double hit_eps, double* out4, uint32_t* flags);
+
 /* Device lexicase selection that replays the reference's random stream:
  * selLexicase (mode 0), selEpsilonLexicase (mode 1, epsilon) and
  * selAutomaticEpsilonLexicase (mode 2; n <= 16384) of deap/tools/
@@ -474,6 +506,9 @@ int gpe_last_geometry_ex(const gpe_ctx* ctx, int64_t* out, int n);
 #define GPE_LAUNCH_MOMENTS 7      /* the last moments run's launch of the exact
                                      D = 5 core's moments kernel ... */
 #define GPE_LAUNCH_MOMENTS_DEEP 8 /* ... and of the exact deep core's */
+#define GPE_LAUNCH_ABSERR 9       /* the last abs-error run's launch of the exact
+                                     D = 5 core's abs-error kernel ... */
+#define GPE_LAUNCH_ABSERR_DEEP 10 /* ... and of the exact deep core's */
 #define GPE_LAUNCH_SHAPE_FIELDS 13
 int gpe_last_launch_shape(const gpe_ctx* ctx, int which, int64_t* out, int n);
 
