@@ -60,6 +60,8 @@ SIGNATURES = {
     "gpe_run_abserr": (_I, [_P, ctypes.c_double, _P, _P, _P]),
     "gpe_run_abserr_device": (_I, [_P, ctypes.c_double, _P, _P, _P]),
     "gpe_host_abserr": (_I, [_P, _P, _I64, _I64, ctypes.c_double, _P, _P]),
+    "gpe_run_abserr_cases": (_I, [_P, ctypes.c_double, _P, _P, _P, _P]),
+    "gpe_host_abserr_cases": (_I, [_P, _P, _I64, _I64, _P]),
     "gpe_lexicase": (_I, [_P, _P, _I64, _I64, _P, _I, ctypes.c_double, _P,
                           _I64, _P, ctypes.POINTER(_I64)]),
     "gpe_set_lowering": (_I, [_P, _I, _I, _P, _I, _P, _I]),
@@ -223,6 +225,21 @@ def host_abserr(f, terms, hit_eps):
     if rc != 0:
         raise GpeError("gpe_host_abserr failed (%d)" % rc)
     return out4, int(flags[0])
+
+
+def host_abserr_cases(f, terms):
+    """Host twin of a cases run's per-case value (CPU, no GPU): one program's
+    per-case values ``f[n]`` against ``terms[n_terms, n]`` → ``e[n]``."""
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    t = np.ascontiguousarray(np.atleast_2d(terms), dtype=np.float64)
+    if f.ndim != 1 or t.shape[1] != len(f):
+        raise ValueError("f is [n] and terms [n_terms, n]")
+    out = np.zeros(len(f), dtype=np.float64)
+    rc = load().gpe_host_abserr_cases(_ptr(f), _ptr(t), t.shape[0], len(f),
+                                      _ptr(out))
+    if rc != 0:
+        raise GpeError("gpe_host_abserr_cases failed (%d)" % rc)
+    return out
 
 
 TRIG_CLASSES = ("general", "mid", "small")
@@ -666,6 +683,28 @@ class Context(object):
                 "gpe_run_abserr")
         return out4, err, flags
 
+    def run_abserr_cases(self, hit_eps, n_cases, want_cases=True):
+        """gpe_run_abserr_cases → (cases float64 [n_prog, n_cases] or None,
+        out4, err, flags): :meth:`run_abserr` that also leaves each case's
+        ``|d|`` in the context's per-case matrix (``lexicase(None, ...)``
+        selects on it).  *want_cases* False: no host copy of the matrix is
+        made or allocated."""
+        n = self.n_prog
+        cases = np.zeros((n, n_cases), dtype=np.float64) if want_cases \
+            else None
+        out4 = np.zeros((n, 4), dtype=np.float64)
+        err = np.full(n, GPE_NO_ERROR, dtype=np.uint64)
+        flags = np.zeros(n, dtype=np.uint32)
+        if n:
+            if n_cases != self.n_cases:
+                raise ValueError("run_abserr_cases: the context holds %d "
+                                 "cases, not %d" % (self.n_cases, n_cases))
+            self._check(self.lib.gpe_run_abserr_cases(
+                self.h, float(hit_eps),
+                _ptr(cases) if want_cases else None, _ptr(out4), _ptr(err),
+                _ptr(flags)), "gpe_run_abserr_cases")
+        return cases, out4, err, flags
+
     def run_abserr_device(self, hit_eps, out4_ptr, err_ptr=None,
                           flags_ptr=None):
         """gpe_run_abserr_device: the results at device addresses (torch
@@ -687,7 +726,7 @@ class Context(object):
 
     def lexicase(self, values, maximise, k, rng, mode=0, epsilon=0.0):
         """gpe_lexicase: k selections on ``values`` [n, n_cases] (None: the
-        last run_cases matrix), drawing from the ``random.Random``-compatible
+        last run_cases / run_abserr_cases matrix), drawing from the ``random.Random``-compatible
         ``rng`` exactly as the reference does and advancing its state.
         Returns (indices, failed): failed is -1 or the selection at which no
         candidate was left (the reference's IndexError)."""

@@ -55,6 +55,14 @@ HD void accumulate(Part& p, uint32_t& flag, double d, double hit_eps) {
   if (e <= hit_eps && e < __builtin_inf()) p.hits += 1.0;
 }
 
+// One case's absolute error as a cases run keeps it (gpe_run_abserr_cases:
+// the asm epilogue, the rows kernel and the host twin): |d|, and the default
+// nan at a case whose call raised (verr: the cores' ValueError bit; a values
+// row already holds nan there, so the rows route and the host pass false).
+HD double case_error(double d, bool verr) {
+  return verr ? __builtin_nan("") : __builtin_fabs(d);
+}
+
 // partial b into partial a (the cross-lane, cross-thread and cross-group
 // steps): add, max, add
 HD void merge(Part& a, const Part& b) {
@@ -116,13 +124,16 @@ __global__ __launch_bounds__(256) void reduce_groups_abserr(
 // chunk of the rows route); terms[n_terms][n_cases] are the staged term
 // columns.  The program's flags are written, not or-ed: a program the asm
 // kernels left for a redo tile is computed here from its first case on.
-__global__ __launch_bounds__(256) void abserr_rows(const double* __restrict__ rows,
-                                                   int64_t n_cases,
-                                                   const double* __restrict__ terms,
-                                                   int n_terms, double hit_eps, int64_t p0,
-                                                   const int32_t* __restrict__ list,
-                                                   double* __restrict__ out4,
-                                                   uint32_t* __restrict__ flags) {
+// (One body, two kernels: abserr_rows, and abserr_rows_cases for a cases run.)
+template <bool CASES>
+__device__ __forceinline__ void abserr_rows_body(const double* __restrict__ rows,
+                                                 int64_t n_cases,
+                                                 const double* __restrict__ terms,
+                                                 int n_terms, double hit_eps, int64_t p0,
+                                                 const int32_t* __restrict__ list,
+                                                 double* __restrict__ out4,
+                                                 uint32_t* __restrict__ flags,
+                                                 double* __restrict__ case_out) {
   __shared__ abserr::Part sh[256];
   __shared__ uint32_t shflag;
   const int64_t prog = list[blockIdx.x];
@@ -134,6 +145,10 @@ __global__ __launch_bounds__(256) void abserr_rows(const double* __restrict__ ro
     double d = r[c];
     for (int q = 0; q < n_terms; ++q) d = d - terms[(size_t)q * (size_t)n_cases + c];
     abserr::accumulate(acc, flag, d, hit_eps);
+    // (the matrix is indexed by the program's own number: only `rows` is
+    // relative to the chunk)
+    if constexpr (CASES)
+      case_out[(size_t)prog * (size_t)n_cases + c] = abserr::case_error(d, false);
   }
   sh[threadIdx.x] = acc;
   __syncthreads();
@@ -154,6 +169,27 @@ __global__ __launch_bounds__(256) void abserr_rows(const double* __restrict__ ro
     o[3] = sh[0].hits;
     flags[prog] = shflag;
   }
+}
+
+__global__ __launch_bounds__(256) void abserr_rows(const double* __restrict__ rows,
+                                                   int64_t n_cases,
+                                                   const double* __restrict__ terms,
+                                                   int n_terms, double hit_eps, int64_t p0,
+                                                   const int32_t* __restrict__ list,
+                                                   double* __restrict__ out4,
+                                                   uint32_t* __restrict__ flags) {
+  abserr_rows_body<false>(rows, n_cases, terms, n_terms, hit_eps, p0, list, out4, flags,
+                          nullptr);
+}
+
+// A cases run's rows kernel: the same reduction, and each case's |d| into
+// case_out[n_prog][n_cases] at the program's own row.
+__global__ __launch_bounds__(256) void abserr_rows_cases(
+    const double* __restrict__ rows, int64_t n_cases, const double* __restrict__ terms,
+    int n_terms, double hit_eps, int64_t p0, const int32_t* __restrict__ list,
+    double* __restrict__ out4, uint32_t* __restrict__ flags, double* __restrict__ case_out) {
+  abserr_rows_body<true>(rows, n_cases, terms, n_terms, hit_eps, p0, list, out4, flags,
+                         case_out);
 }
 
 }  // namespace

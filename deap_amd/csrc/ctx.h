@@ -458,6 +458,14 @@ struct gpe_ctx {
   uint32_t* d_jump_a[2] = {};
   Launch aasm, aasm_deep;
   double hit_eps = 0.0;
+  // A cases run (gpe_run_abserr_cases): the same run with the kernels' cases
+  // variants (jump_ac) and abserr_rows_cases, which also write each case's
+  // |d| into d_case_out.  abs_cases is the request: it outlives the rows
+  // route's chunk loop (whose values runs set and clear case_on themselves)
+  // and is cleared by the entry point on every way out.
+  std::vector<uint32_t> jump_ac[2];
+  uint32_t* d_jump_ac[2] = {};
+  int abs_cases = 0;
   double* d_abs = nullptr;
   size_t abs_cap = 0;
   char* h_pin_vals = nullptr;        // pinned staging of gpe_run_values' copy back

@@ -178,12 +178,14 @@ int run_exact_asm(gpe_ctx* ctx, const std::vector<int32_t>& rx, double* hi,
 // appended to `rest` whole: its sums here are incomplete.
 // epi = kEpiAbsErr: the abs-error kernels instead (jump_a, aasm / aasm_deep,
 // two accumulator pairs, reduce_groups_abserr into out[n_prog][4], the
-// GPE_FLAG_*_TERM bits into flags).
+// GPE_FLAG_*_TERM bits into flags); epi = kEpiAbsErrCases: those kernels'
+// cases variants (jump_ac), the same plans.
 int run_moments_asm(gpe_ctx* ctx, const std::vector<int32_t>& rx,
                     const std::vector<int32_t>& rxd, double* out6, unsigned long long* err,
                     uint32_t* flags, std::vector<int32_t>& rest, int epi = kEpiMoments) {
-  const bool abs_run = epi == kEpiAbsErr;
-  uint32_t* const* const d_jump = abs_run ? ctx->d_jump_a : ctx->d_jump_m;
+  const bool abs_run = epi == kEpiAbsErr || epi == kEpiAbsErrCases;
+  uint32_t* const* const d_jump = epi == kEpiAbsErrCases ? ctx->d_jump_ac
+                                  : abs_run ? ctx->d_jump_a : ctx->d_jump_m;
   Launch& L5 = abs_run ? ctx->aasm : ctx->masm;
   Launch& Ld = abs_run ? ctx->aasm_deep : ctx->masm_deep;
   const int accw = abs_run ? 2 : 3;

@@ -1,6 +1,7 @@
-// The body of f_eval_asm, f_eval_asm_values, f_eval_asm_moments and
-// f_eval_asm_abserr (asm_kernels.h includes this file inside each of the four
-// kernel templates, after `constexpr int EPILOGUE`): one text, four kernels.  The fitness kernel is compiled from exactly the
+// The body of f_eval_asm, f_eval_asm_values, f_eval_asm_moments,
+// f_eval_asm_abserr and f_eval_asm_abserr_cases (asm_kernels.h includes this
+// file inside each of the five kernel templates, after
+// `constexpr int EPILOGUE`): one text, five kernels.  The fitness kernel is compiled from exactly the
 // text it always had (its VALUES branch is discarded), so its registers do not
 // depend on the values epilogue; each kernel holds its own copy of its core
 // and has its own jump table (init_asm).
@@ -9,7 +10,10 @@
 // slots.  Same geometry, staging, epilogue and redo.
   [[maybe_unused]] constexpr bool VALUES = EPILOGUE == kEpiValues;
   [[maybe_unused]] constexpr bool MOMENTS = EPILOGUE == kEpiMoments;
-  [[maybe_unused]] constexpr bool ABSERR = EPILOGUE == kEpiAbsErr;
+  [[maybe_unused]] constexpr bool ABSERR =
+      EPILOGUE == kEpiAbsErr || EPILOGUE == kEpiAbsErrCases;
+  // a cases run's abs-error kernels: each valid case's |d| to case_out too
+  [[maybe_unused]] constexpr bool ABSCASES = EPILOGUE == kEpiAbsErrCases;
   // accumulator pairs per program and lane (moments: f, f f, f y; abs error:
   // the sum of |d|, then (max |d|, hits))
   constexpr int ACCW = MOMENTS ? 3 : ABSERR ? 2 : 1;
@@ -275,6 +279,11 @@
             if ((vbits >> k) & 1u)
               verr_at = min(verr_at, ((unsigned long long)c << 2) | GPE_ERR_VALUE);
             abserr::accumulate(p, flag, dlt, a.hit_eps);
+            // (f_eval_asm_abserr_cases: nan at a ValueError case, as a values
+            // run stores it; pad lanes store nothing)
+            if constexpr (ABSCASES)
+              a.case_out[(size_t)prog * a.n_cases + c] =
+                  abserr::case_error(dlt, ((vbits >> k) & 1u) != 0);
           }
         }
         ac[0] = p.hi;

@@ -1242,6 +1242,11 @@ int init_asm(gpe_ctx* ctx) {
                   ctx->asm_exact_table, ctx->jump_a[0], "abs-error exact asm")) ||
       (rc = jumps(eval_probe(f_eval_asm_abserr<false, true, true>, true, false),
                   ctx->asm_exact_deep_table, ctx->jump_a[1], "abs-error exact deep asm")) ||
+      (rc = jumps(eval_probe(f_eval_asm_abserr_cases<false, false, true>, true, false, true),
+                  ctx->asm_exact_table, ctx->jump_ac[0], "abs-error cases exact asm")) ||
+      (rc = jumps(eval_probe(f_eval_asm_abserr_cases<false, true, true>, true, false, true),
+                  ctx->asm_exact_deep_table, ctx->jump_ac[1],
+                  "abs-error cases exact deep asm")) ||
       (rc = jumps([&](uint32_t* d) {
                     constexpr int K = asmcore_typed::K;
                     AsmTask t{};
@@ -1308,7 +1313,8 @@ int init_asm(gpe_ctx* ctx) {
   for (int k = 0; k < kJvCount; ++k)
     if (upload(ctx->jump_v[k], &ctx->d_jump_v[k])) return GPE_E_HIP;
   for (int k = 0; k < 2; ++k)
-    if (upload(ctx->jump_m[k], &ctx->d_jump_m[k]) || upload(ctx->jump_a[k], &ctx->d_jump_a[k]))
+    if (upload(ctx->jump_m[k], &ctx->d_jump_m[k]) || upload(ctx->jump_a[k], &ctx->d_jump_a[k]) ||
+        upload(ctx->jump_ac[k], &ctx->d_jump_ac[k]))
       return GPE_E_HIP;
   ctx->asm_ready = true;
   return 0;
@@ -1819,7 +1825,7 @@ void gpe_destroy(gpe_ctx* ctx) {
                   ctx->masm.d_slot_prog, ctx->masm.d_part, ctx->masm_deep.d_slot_prog,
                   ctx->masm_deep.d_part, ctx->d_jump_a[0], ctx->d_jump_a[1], ctx->d_abs,
                   ctx->aasm.d_slot_prog, ctx->aasm.d_part, ctx->aasm_deep.d_slot_prog,
-                  ctx->aasm_deep.d_part};
+                  ctx->aasm_deep.d_part, ctx->d_jump_ac[0], ctx->d_jump_ac[1]};
   if (ctx->comm && rccl().ok) (void)rccl().comm_destroy(ctx->comm);
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -2804,15 +2810,17 @@ int moments_check(gpe_ctx* ctx) {
 // that range alone (plan_mode's sub_lo / sub_hi / sub_mask), moments_rows on
 // them.  d_err / d_flags: device arrays of n_prog entries.
 // An abs-error run (run_abserr) takes the same two routes with its own
-// kernels (epi = kEpiAbsErr), results array and reducer: `d_out` is the
+// kernels (epi = kEpiAbsErr; a cases run: kEpiAbsErrCases), results array and
+// reducer: `d_out` is the
 // per-program results array of the run, `reduce(p0, list, m)` the rows
 // route's reducer on a chunk's m listed programs, whose rows start at p0.
 int run_routes(gpe_ctx* ctx, unsigned long long* d_err, uint32_t* d_flags, int epi,
                double* d_out,
                const std::function<void(int64_t, const int32_t*, int64_t)>& reduce) {
   const int64_t np = ctx->n_prog, nc = ctx->n_cases;
-  Launch& L5 = epi == kEpiAbsErr ? ctx->aasm : ctx->masm;
-  Launch& Ld = epi == kEpiAbsErr ? ctx->aasm_deep : ctx->masm_deep;
+  const bool abs_run = epi == kEpiAbsErr || epi == kEpiAbsErrCases;
+  Launch& L5 = abs_run ? ctx->aasm : ctx->masm;
+  Launch& Ld = abs_run ? ctx->aasm_deep : ctx->masm_deep;
   HIPCHK(hipMemsetAsync(d_err, 0xff, (size_t)np * sizeof(unsigned long long), ctx->stream));
   HIPCHK(hipMemsetAsync(d_flags, 0, (size_t)np * sizeof(uint32_t), ctx->stream));
   // the two routes' programs
@@ -2907,11 +2915,21 @@ int run_moments(gpe_ctx* ctx, unsigned long long* d_err, uint32_t* d_flags) {
 
 // The abs-error words of the loaded programs into ctx->d_abs: the moments
 // run's routes (run_routes) with the abs-error kernels and abserr_rows, which
-// subtracts the staged term columns from the chunk's values.
+// subtracts the staged term columns from the chunk's values.  With
+// ctx->abs_cases (gpe_run_abserr_cases) both routes also write every case's
+// |d| into d_case_out, each program's row by the route that gives its words.
 int run_abserr(gpe_ctx* ctx, double hit_eps, unsigned long long* d_err, uint32_t* d_flags) {
   const int64_t nc = ctx->n_cases;
   if (ensure(ctx, &ctx->d_abs, &ctx->abs_cap, 4 * (size_t)ctx->n_prog)) return GPE_E_HIP;
   ctx->hit_eps = hit_eps;
+  if (ctx->abs_cases)
+    return run_routes(ctx, d_err, d_flags, kEpiAbsErrCases, ctx->d_abs,
+                      [&](int64_t p0, const int32_t* list, int64_t m) {
+                        hipLaunchKernelGGL(abserr_rows_cases, dim3((unsigned)m), dim3(256), 0,
+                                           ctx->stream, (const double*)ctx->d_mrows, nc,
+                                           (const double*)ctx->d_terms, ctx->nt, hit_eps, p0,
+                                           list, ctx->d_abs, d_flags, ctx->d_case_out);
+                      });
   return run_routes(ctx, d_err, d_flags, kEpiAbsErr, ctx->d_abs,
                     [&](int64_t p0, const int32_t* list, int64_t m) {
                       hipLaunchKernelGGL(abserr_rows, dim3((unsigned)m), dim3(256), 0,
@@ -2967,11 +2985,11 @@ int gpe_run_abserr_device(gpe_ctx* ctx, double hit_eps, void* d_out4, void* d_er
   return 0;
 }
 
-int gpe_run_abserr(gpe_ctx* ctx, double hit_eps, double* out4, uint64_t* first_err,
+namespace {
+// gpe_run_abserr and gpe_run_abserr_cases: the run, then the per-program
+// results through the pinned staging
+int abserr_to_host(gpe_ctx* ctx, double hit_eps, double* out4, uint64_t* first_err,
                    uint32_t* flags) {
-  if (!ctx || !out4) return GPE_E_INVALID;
-  if (int rc = abserr_check(ctx, hit_eps)) return rc;
-  HIPCHK(hipSetDevice(ctx->device));
   if (int rc = moments_side_buffers(ctx)) return rc;
   if (int rc = run_abserr(ctx, hit_eps, ctx->d_mom_err, ctx->d_mom_flags)) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -2983,6 +3001,33 @@ int gpe_run_abserr(gpe_ctx* ctx, double hit_eps, double* out4, uint64_t* first_e
     if (int rc = values_to_host(ctx, flags, ctx->d_mom_flags, np * sizeof(uint32_t))) return rc;
   return 0;
 }
+}  // namespace
+
+int gpe_run_abserr(gpe_ctx* ctx, double hit_eps, double* out4, uint64_t* first_err,
+                   uint32_t* flags) {
+  if (!ctx || !out4) return GPE_E_INVALID;
+  if (int rc = abserr_check(ctx, hit_eps)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  return abserr_to_host(ctx, hit_eps, out4, first_err, flags);
+}
+
+int gpe_run_abserr_cases(gpe_ctx* ctx, double hit_eps, double* out_cases, double* out4,
+                         uint64_t* first_err, uint32_t* flags) {
+  if (!ctx || !out4) return GPE_E_INVALID;
+  if (int rc = abserr_check(ctx, hit_eps)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t n = (size_t)ctx->n_prog * (size_t)ctx->n_cases;
+  if (ensure(ctx, &ctx->d_case_out, &ctx->case_cap, n)) return GPE_E_HIP;
+  // whatever way the run is left, the next abs-error run is a plain one
+  struct Request {
+    gpe_ctx* c;
+    ~Request() { c->abs_cases = 0; }
+  } request{ctx};
+  ctx->abs_cases = 1;
+  if (int rc = abserr_to_host(ctx, hit_eps, out4, first_err, flags)) return rc;
+  if (out_cases) return values_to_host(ctx, out_cases, ctx->d_case_out, n * sizeof(double));
+  return 0;
+}
 
 int gpe_host_abserr(const double* f, const double* terms, int64_t n_terms, int64_t n_cases,
                     double hit_eps, double* out4, uint32_t* flags) {
@@ -2990,6 +3035,18 @@ int gpe_host_abserr(const double* f, const double* terms, int64_t n_terms, int64
     return GPE_E_INVALID;
   if (!(hit_eps >= 0.0)) return GPE_E_ARG;
   abserr::host_row(f, terms, n_terms, n_cases, hit_eps, out4, flags);
+  return 0;
+}
+
+int gpe_host_abserr_cases(const double* f, const double* terms, int64_t n_terms,
+                          int64_t n_cases, double* out_cases) {
+  if (!f || (n_terms > 0 && !terms) || n_terms < 0 || n_cases <= 0 || !out_cases)
+    return GPE_E_INVALID;
+  for (int64_t c = 0; c < n_cases; ++c) {
+    double d = f[c];
+    for (int64_t q = 0; q < n_terms; ++q) d = d - terms[q * n_cases + c];
+    out_cases[c] = abserr::case_error(d, false);
+  }
   return 0;
 }
 

@@ -355,9 +355,10 @@ int launch_f(gpe_ctx* ctx, Launch& L, bool deep, unsigned long long* err,
 int launch_asm(gpe_ctx* ctx, Launch& L, unsigned long long* err,
                uint32_t* flags, bool deep_core = false, bool exact = false,
                int epi = kEpiFitness) {
-  // (epi: kEpiMoments / kEpiAbsErr pick those runs' kernels; a values run is
-  // ctx->values_on)
-  const bool moments = epi == kEpiMoments, abserr = epi == kEpiAbsErr;
+  // (epi: kEpiMoments / kEpiAbsErr / kEpiAbsErrCases pick those runs' kernels;
+  // a values run is ctx->values_on)
+  const bool moments = epi == kEpiMoments, abs_cases = epi == kEpiAbsErrCases,
+             abserr = epi == kEpiAbsErr || abs_cases;
   if (L.n_slots == 0) return 0;
   AsmTask a{};
   a.code = exact ? ctx->d_acode_x : ctx->d_acode;
@@ -375,6 +376,9 @@ int launch_asm(gpe_ctx* ctx, Launch& L, unsigned long long* err,
   a.tiles_per_group = L.tiles_per_group;
   a.part = L.d_part;
   a.case_out = case_dst(ctx);
+  // (a cases run of the abs-error kernels: the matrix itself, whatever
+  // case_on says — the rows route's values runs set and clear that)
+  if (abs_cases) a.case_out = ctx->d_case_out;
   a.first_err = err;
   a.flags = flags;
   a.redo = ctx->d_redo;
@@ -421,8 +425,12 @@ int launch_asm(gpe_ctx* ctx, Launch& L, unsigned long long* err,
   if (abserr) {                // the exact cores' abs-error kernels (jump_a)
     if (!exact || f32 || ctx->values_on)
       return fail(ctx, GPE_E_STATE, "abs-error kernels: exact fp64 cores");
-    kern = deep_core ? f_eval_asm_abserr<false, true, true>
-                     : f_eval_asm_abserr<false, false, true>;
+    if (abs_cases && !a.case_out)
+      return fail(ctx, GPE_E_STATE, "abs-error cases kernels: no per-case matrix");
+    kern = abs_cases ? (deep_core ? f_eval_asm_abserr_cases<false, true, true>
+                                  : f_eval_asm_abserr_cases<false, false, true>)
+                     : (deep_core ? f_eval_asm_abserr<false, true, true>
+                                  : f_eval_asm_abserr<false, false, true>);
   }
   HIPCHK(hipFuncSetAttribute((const void*)kern,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -121,10 +121,10 @@ def _check_shardable(spec, case_sharded):
                                   "moments are additive over case shards, "
                                   "but no sharded moments run is built")
     if getattr(spec, "abs_error", False):
-        raise NotImplementedError("SymbRegAbsError runs on one GPU: the sum, "
+        raise NotImplementedError("%s runs on one GPU: the sum, "
                                   "the max and the hits combine over case "
                                   "shards, but no sharded abs-error run is "
-                                  "built")
+                                  "built" % type(spec).__name__)
     if getattr(spec, "per_case", False):
         raise NotImplementedError("per-case outputs are not gathered across "
                                   "ranks; evaluate per-case specs on one GPU")

@@ -26,6 +26,7 @@ constant subtree raised).
 """
 import math
 import os
+import random
 import time
 import warnings
 from functools import partial
@@ -47,6 +48,7 @@ def _tuples1(values, as_int):
 
 __all__ = ["SymbRegMSE", "SymbRegNumpySSE", "SymbRegSumSSE",
            "SymbRegScaledMSE", "SymbRegAbsError", "SymbRegCaseErrors",
+           "SymbRegCaseAbsErrors",
            "BooleanHits",
            "exact_dd_sums",
            "TypedBoolHits", "GPUEvaluator", "gpu_map", "pack_bitplanes",
@@ -331,6 +333,49 @@ class SymbRegAbsError(SymbRegMSE):
         return out
 
 
+class SymbRegCaseAbsErrors(SymbRegAbsError):
+    """Per-case absolute errors ``e_c = abs(f(*row_c) - t0_c - t1_c - ...)``
+    for epsilon-lexicase selection, with :class:`SymbRegAbsError`'s summaries
+    from the same GPU pass (``gpe_run_abserr_cases``).  Automatic
+    epsilon-lexicase takes its epsilon from the median absolute deviation of a
+    case's errors, which does not commute with squaring: selection on these
+    differs from selection on :class:`SymbRegCaseErrors`' squared errors.
+
+    *cases* ``"host"`` (default): an individual's fitness is
+    ``tuple(e_0 ... e_{n-1})``, one value per case (weights
+    ``(-1.0,) * n_cases``), as :class:`SymbRegCaseErrors` returns squared
+    ones; ``tools.selLexicase*`` and ``tools.sel*LexicaseGPU`` select on it
+    unchanged.  ``"device"``: no ``n x n_cases`` copy is made; the matrix
+    stays on the GPU for :meth:`GPUEvaluator.select_lexicase` and the fitness
+    tuple is the summary *fitness* names, as in :class:`SymbRegAbsError`.
+    Either way ``last_mae``, ``last_max_error`` and ``last_hits`` are filled,
+    :meth:`GPUEvaluator.select_lexicase` works, and exceptions and refusals
+    are :class:`SymbRegAbsError`'s."""
+    abs_cases = True
+
+    def __init__(self, X, terms, hit_eps=0.01, cases="host",
+                 fitness=("mae",)):
+        SymbRegAbsError.__init__(self, X, terms, hit_eps, fitness)
+        if cases not in ("host", "device"):
+            raise ValueError("cases must be 'host' or 'device' (got %r)"
+                             % (cases,))
+        self.cases = cases
+
+    def finish(self, i, w4, lo, err, flags, cases=None):
+        res = SymbRegAbsError.finish(self, i, w4, lo, err, flags)
+        if self.cases == "device" or isinstance(res, BaseException):
+            return res
+        return tuple(np.asarray(cases, dtype=np.float64).tolist())
+
+    def finish_all(self, w4, lo, err, flags, cases=None):
+        out = SymbRegAbsError.finish_all(self, w4, lo, err, flags)
+        if self.cases == "device":
+            return out
+        rows = np.asarray(cases, dtype=np.float64).tolist()
+        return [res if isinstance(res, BaseException) else tuple(row)
+                for res, row in zip(out, rows)]
+
+
 def _check_scaled_setup(spec, pset, flattener, precision):
     """A moments-route spec's evaluator (linear scaling, absolute error): what
     it refuses, and why."""
@@ -606,6 +651,10 @@ class GPUEvaluator(object):
         self.last_mae = np.zeros(0)
         self.last_max_error = np.zeros(0)
         self.last_hits = np.zeros(0, dtype=np.int64)
+        # select_lexicase: the individuals (kept, so that their identities
+        # stay theirs) and results of the last evaluation that left a
+        # per-case matrix on the GPU
+        self._lex_batch = None
 
     def close(self):
         """Release the device contexts (the evaluator's and predict's)."""
@@ -854,7 +903,12 @@ class GPUEvaluator(object):
             self.last_scaling = (a, b)
         elif getattr(self.spec, "abs_error", False):
             # (the four words per program in hi's place)
-            hi, err, flags = self.ctx.run_abserr(self.spec.hit_eps)
+            if getattr(self.spec, "abs_cases", False):
+                cases, hi, err, flags = self.ctx.run_abserr_cases(
+                    self.spec.hit_eps, self.spec.n_cases,
+                    want_cases=self.spec.cases == "host")
+            else:
+                hi, err, flags = self.ctx.run_abserr(self.spec.hit_eps)
             lo = np.zeros(len(err))
             self.last_mae, self.last_max_error, self.last_hits = \
                 self.spec.figures(hi, err, flags)
@@ -894,13 +948,18 @@ class GPUEvaluator(object):
         self.stats["individuals"] += len(individuals)
         self.stats["node_evals"] += batch.n_nodes() * \
             self.spec.n_cases
-        if cases is None and hasattr(self.spec, "finish_all"):
-            out = self.spec.finish_all(*[None if x is None else np.asarray(x)
-                                         for x in (hi, lo, err, flags)])
+        abs_cases = getattr(self.spec, "abs_cases", False)
+        if (cases is None or abs_cases) and hasattr(self.spec, "finish_all"):
+            args = [None if x is None else np.asarray(x)
+                    for x in (hi, lo, err, flags)]
+            out = self.spec.finish_all(*args, cases=cases) if abs_cases \
+                else self.spec.finish_all(*args)
             if getattr(batch, "any_err", True):
                 for i in np.flatnonzero(batch.err).tolist():
                     out[i] = SyntaxError("too many nested parentheses") \
                         if batch.err[i] == ERR_SYNTAX else batch.const_exc[i]
+            if abs_cases:
+                self._lex_batch = (list(individuals), out)
             return out
         out = []
         for i in range(len(individuals)):
@@ -915,7 +974,64 @@ class GPUEvaluator(object):
             else:
                 out.append(self.spec.finish(i, hi[i], lo[i], err[i],
                                             flags[i]))
+        if cases is not None:
+            self._lex_batch = (list(individuals), out)
         return out
+
+    LEXICASE_MODES = {"plain": 0, "epsilon": 1, "automatic": 2}
+
+    def select_lexicase(self, individuals, k, mode="automatic", epsilon=0.0):
+        """Lexicase selection of *k* individuals straight from the per-case
+        matrix the last :meth:`evaluate` / :meth:`map` left on the GPU
+        (:class:`SymbRegCaseAbsErrors` in either *cases* mode,
+        :class:`SymbRegCaseErrors`): ``gpe_lexicase`` without a host round
+        trip.  *mode* ``"plain"``, ``"epsilon"`` (with *epsilon*) or
+        ``"automatic"``: ``tools.selLexicase``, ``selEpsilonLexicase`` and
+        ``selAutomaticEpsilonLexicase`` with every case minimised; the draws
+        come from the module ``random`` stream as theirs do, so a seeded run
+        selects the same individuals and leaves the same state.
+
+        *individuals* must be the batch of that last evaluation: the same
+        objects in the same order (``ValueError`` otherwise).  If an
+        individual of the batch raised, its exception is raised here, the
+        first in order.  The device selection's limits (16,384 individuals
+        for ``"automatic"``; ``n/32 + n_cases`` words within 48 KiB of LDS)
+        are raised as the library words them."""
+        if mode not in self.LEXICASE_MODES:
+            raise ValueError("mode must be 'plain', 'epsilon' or 'automatic' "
+                             "(got %r)" % (mode,))
+        individuals = list(individuals)
+        if self._lex_batch is None:
+            raise ValueError(
+                "select_lexicase: this evaluator's last evaluate / map left "
+                "no per-case matrix on the GPU (its spec is %s; evaluate "
+                "with SymbRegCaseAbsErrors or SymbRegCaseErrors first)"
+                % type(self.spec).__name__)
+        last, results = self._lex_batch
+        if len(individuals) != len(last) or \
+                any(a is not b for a, b in zip(individuals, last)):
+            raise ValueError(
+                "select_lexicase: individuals must be the batch of this "
+                "evaluator's last evaluate / map, the same objects in the "
+                "same order: the GPU holds that batch's per-case errors")
+        if self.ctx.n_prog != len(last):
+            raise ValueError(
+                "select_lexicase: the context now holds %d programs, not the "
+                "%d of the last evaluate / map; evaluate the batch again"
+                % (self.ctx.n_prog, len(last)))
+        for res in results:
+            if isinstance(res, BaseException):
+                raise res
+        if k == 0:                        # the reference's loop runs 0 times
+            return []
+        if not individuals:               # individuals[0] in the reference
+            raise IndexError("list index out of range")
+        idx, failed = self.ctx.lexicase(
+            None, np.zeros(self.spec.n_cases, dtype=np.uint8), k,
+            random._inst, self.LEXICASE_MODES[mode], epsilon)
+        if failed >= 0:                   # random.choice([]) in the reference
+            raise IndexError("Cannot choose from an empty sequence")
+        return [individuals[i] for i in idx.tolist()]
 
     def map(self, individuals):
         return _yield_until_error(self.evaluate(list(individuals)))

@@ -236,6 +236,34 @@ int gpe_run_abserr(gpe_ctx* ctx, double hit_eps, double* out4, uint64_t* first_e
 int gpe_run_abserr_device(gpe_ctx* ctx, double hit_eps, void* d_out4, void* d_err,
                           void* d_flags);
 
+/* A cases run: gpe_run_abserr that also writes every program's per-case
+ * absolute error e_c = |f(*row_c) - t0_c - t1_c - ...| (the terms subtracted
+ * left to right: the e the sums above are made of) into the context's
+ * per-case matrix double[n_prog][n_cases], the one gpe_run_cases fills with
+ * squared errors.  out4, first_err and flags are gpe_run_abserr's, from the
+ * same pass, bit for bit.  out_cases: the HOST copy double[n_prog][n_cases]
+ * (through pinned staging), or NULL to leave the matrix on the device only,
+ * where gpe_lexicase(ctx, NULL, ...) selects on it.  An erroring case of the
+ * exact cores holds nan; a program of the rows route holds nan at least at
+ * its first erroring case.  Every row is written whole by one route (a
+ * program the abs-error kernels leave for a redo is rewritten by the rows
+ * route).  Refusals and codes as gpe_run_abserr.
+ * Residency: a cases run replaces the per-case matrix, as gpe_run_cases does;
+ * a plain gpe_run_abserr, a moments run and a values run leave it untouched;
+ * the resident fitness (gpe_tournament(NULL)) is untouched by both abs-error
+ * runs.  Launch plans, P and LDS are gpe_run_abserr's (GPE_LAUNCH_ABSERR,
+ * GPE_LAUNCH_ABSERR_DEEP).
+ * Replaces: predict, abs(... - y) on the host and a second pass for the
+ * summaries, before epsilon-lexicase on absolute errors. */
+int gpe_run_abserr_cases(gpe_ctx* ctx, double hit_eps, double* out_cases, double* out4,
+                         uint64_t* first_err, uint32_t* flags);
+
+/* Host twin of a cases run's per-case value (no GPU): out_cases[n_cases] of
+ * one row f[n_cases] against terms[n_terms][n_cases], the same per-case
+ * function in a plain loop. */
+int gpe_host_abserr_cases(const double* f, const double* terms, int64_t n_terms,
+                          int64_t n_cases, double* out_cases);
+
 /* Host twin of the rows route's reduction (no GPU): the four words and the
  * flags of one row f[n_cases] of per-case values against
  * terms[n_terms][n_cases], in abserr_rows' order (256 strided partials, the
@@ -248,8 +276,8 @@ int gpe_host_abserr(const double* f, const double* terms, int64_t n_terms, int64
  * selAutomaticEpsilonLexicase (mode 2; n <= 16384) of deap/tools/
  * selection.py:214-320.  values is a HOST double[n][n_cases]
  * (fitness.values per individual), or NULL to select on the per-case
- * matrix of the last gpe_run_cases (n = programs) without a host round
- * trip.  maximise[n_cases]: 1 where the case's weight is positive.
+ * matrix of the last gpe_run_cases or gpe_run_abserr_cases (n = programs)
+ * without a host round trip.  maximise[n_cases]: 1 where the case's weight is positive.
  * mt_state[625] (in/out): CPython's MT19937 state as random.getstate()[1]
  * gives it (624 words, then the position); the kernel makes the
  * reference's draws — random.shuffle(cases), then random.choice(candidates),
