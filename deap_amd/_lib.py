@@ -43,6 +43,8 @@ SIGNATURES = {
     "gpe_device_info": (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I),
                              ctypes.c_char_p, ctypes.c_size_t]),
     "gpe_set_cases": (_I, [_P, _I, _P, _I, _I64, _P, _I]),
+    "gpe_select_cases": (_I, [_P, _P, _I64]),
+    "gpe_case_subset": (_I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     "gpe_set_trig_leaves": (_I, [_P, _I]),
     "gpe_set_precision": (_I, [_P, _I]),
     "gpe_load_programs": (_I, [_P, _P, _I64, _P, _I64, _P]),
@@ -478,12 +480,36 @@ class Context(object):
         self.n_cases = int(n_cases)
         self._keep = (X, terms)
 
+    def select_cases(self, idx):
+        """gpe_select_cases: run on rows *idx* (int64, validated by the
+        library) of the uploaded cases; None: the full set again.  The loaded
+        programs stay loaded."""
+        if idx is None:
+            rc = self.lib.gpe_select_cases(self.h, None, 0)
+        else:
+            idx = np.ascontiguousarray(idx, dtype=np.int64)
+            rc = self.lib.gpe_select_cases(self.h, _ptr(idx), len(idx))
+        self._check(rc, "gpe_select_cases")
+        self.n_cases = self.case_subset()[0]
+
+    def case_subset(self):
+        """gpe_case_subset → (active case count, full case count, whether a
+        subset is active)."""
+        m, full = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self.lib.gpe_case_subset(self.h, ctypes.byref(m),
+                                             ctypes.byref(full)),
+                    "gpe_case_subset")
+        return (m.value if m.value >= 0 else full.value, full.value,
+                m.value >= 0)
+
     def set_trig_leaves(self, enable):
         """Device columns sin(x_v), cos(x_v) per run (see gpeval.h)."""
         self._check(self.lib.gpe_set_trig_leaves(self.h, int(bool(enable))),
                     "gpe_set_trig_leaves")
         self.n_prog = 0
         self.resident = None
+        if self.machine is not None:      # (an active case subset is dropped)
+            self.n_cases = self.case_subset()[0]
 
     def set_precision(self, prec):
         """GPE_PREC_F64 (default) or GPE_PREC_F32 for the F machine."""

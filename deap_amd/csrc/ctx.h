@@ -215,6 +215,25 @@ struct gpe_ctx {
   int trig_leaves = 0;              // columns [nv_user, 3 nv_user):
                                     // sin(x_v), cos(x_v) per run
   int64_t n_cases = 0, n_units = 0;
+  // a case subset (case_subset.h, gpe_select_cases): cs_m >= 0 while one is
+  // active.  d_X / d_terms / n_cases / n_units / label_true then name the
+  // gathered set (d_cs_X, d_cs_terms: grown on need, column stride cs_m) and
+  // the cs_full_* fields keep what gpe_set_cases uploaded.  (sub_lo / sub_hi /
+  // sub_mask below are a subset of the programs, not of the cases.)
+  int64_t cs_m = -1;
+  void* cs_full_X = nullptr;
+  void* cs_full_terms = nullptr;
+  int64_t cs_full_cases = 0, cs_full_units = 0, cs_full_label_true = 0;
+  char* d_cs_X = nullptr;
+  size_t cs_X_cap = 0;
+  char* d_cs_terms = nullptr;
+  size_t cs_terms_cap = 0;
+  int64_t* d_cs_idx = nullptr;
+  size_t cs_idx_cap = 0;
+  unsigned long long* d_cs_count = nullptr;   // the gathered labels' truths
+  // d_case_out holds no matrix of the current case set (a subset was selected
+  // or dropped since the run that wrote it): gpe_lexicase(NULL) refuses
+  bool case_stale = false;
   // programs (flattener format)
   uint32_t* d_code = nullptr;
   size_t code_cap = 0;

@@ -277,7 +277,7 @@ int run_exact_host(gpe_ctx* ctx, int mode, const std::vector<int64_t>& ents, dou
   if (ents.empty()) return 0;
   const int64_t nc = ctx->n_cases;
   const int nvu = ctx->nv_user, nt = ctx->nt;
-  if (!ctx->ex_hcases) {                 // the cases, once per gpe_set_cases
+  if (!ctx->ex_hcases) {                 // the cases, once per gpe_set_cases / gpe_select_cases
     ctx->ex_hX.resize((size_t)nvu * nc);
     ctx->ex_hT.resize((size_t)nt * nc);
     if (nvu) HIPCHK(hipMemcpy(ctx->ex_hX.data(), ctx->d_X, ctx->ex_hX.size() * sizeof(double),

@@ -14,7 +14,8 @@
 // ctx.h (the context and launch plans), fb_kernels.h (the C++ F and B
 // interpreters), asm_kernels.h (the kernels around the generated cores),
 // planner.h (launch geometry, plan(), the launches), exact_run.h (the
-// glibc-exact and exact-int passes); this file holds the device lowering,
+// glibc-exact and exact-int passes), case_subset.h (gpe_select_cases: the
+// device gather of a case subset); this file holds the device lowering,
 // the threaded-code translation, the run paths and the C ABI.
 //
 // Execution model:
@@ -1458,6 +1459,7 @@ int launch_cpp(gpe_ctx* ctx, int mode, Launch& fastL, Launch& deepL,
 
 }  // namespace
 #include "exact_run.h"
+#include "case_subset.h"
 namespace {
 
 int run_common(gpe_ctx* ctx, int mode, double* hi, double* lo,
@@ -1788,7 +1790,9 @@ int gpe_create(int device, gpe_ctx** out) {
 void gpe_destroy(gpe_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
-  void* bufs[] = {ctx->d_X, ctx->d_terms, ctx->d_code, ctx->d_off,
+  subset_drop(ctx);            // (d_X / d_terms: the full set's buffers again)
+  void* bufs[] = {ctx->d_cs_X, ctx->d_cs_terms, ctx->d_cs_idx, ctx->d_cs_count,
+                  ctx->d_X, ctx->d_terms, ctx->d_code, ctx->d_off,
                   ctx->fast.d_slot_prog, ctx->fast.d_part,
                   ctx->deep.d_slot_prog, ctx->deep.d_part,
                   ctx->fasm.d_slot_prog, ctx->fasm.d_part,
@@ -1876,7 +1880,8 @@ int gpe_device_info(const gpe_ctx* ctx, int* n_cu, int* clock_khz, char* name,
 int gpe_set_cases(gpe_ctx* ctx, int machine, const void* X, int n_vars,
                   int64_t n_cases, const void* terms, int n_terms) {
   if (!ctx) return GPE_E_INVALID;
-  ctx->last_mode = -1;         // resident fitness no longer matches
+  subset_drop(ctx);            // an active case subset belongs to the old cases
+  ctx->last_mode = -1;       // resident fitness no longer matches
   ctx->n_exact = 0;            // the exact pass belongs to a population
   ctx->ex_all = 0;
   if (machine != GPE_MACHINE_F && machine != GPE_MACHINE_B)
@@ -1973,8 +1978,25 @@ int gpe_set_cases(gpe_ctx* ctx, int machine, const void* X, int n_vars,
   return 0;
 }
 
+int gpe_select_cases(gpe_ctx* ctx, const int64_t* idx, int64_t m) {
+  if (!ctx) return GPE_E_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  return select_cases(ctx, idx, m);
+}
+
+int gpe_case_subset(const gpe_ctx* ctx, int64_t* m, int64_t* n_full) {
+  if (!ctx) return GPE_E_INVALID;
+  if (m) *m = ctx->cs_m;
+  if (n_full) *n_full = ctx->cs_m >= 0 ? ctx->cs_full_cases : ctx->n_cases;
+  return 0;
+}
+
 int gpe_set_trig_leaves(gpe_ctx* ctx, int enable) {
   if (!ctx) return GPE_E_INVALID;
+  if (ctx->cs_m >= 0) {        // the leaf columns are added to the full set
+    subset_drop(ctx);
+    subset_changed(ctx);
+  }
   ctx->last_mode = -1;         // resident fitness no longer matches
   if (ctx->machine != GPE_MACHINE_F)
     return fail(ctx, GPE_E_STATE, "trig leaves need F-machine cases");
@@ -2529,6 +2551,7 @@ int run_numpy(gpe_ctx* ctx, int mode, double* hi, double* lo,
   if (ctx->n_prog <= 0) return run_common(ctx, GPE_MODE_MSE, hi, lo, err, flags);
   const size_t n = (size_t)ctx->n_prog * (size_t)ctx->n_cases;
   if (ensure(ctx, &ctx->d_case_out, &ctx->case_cap, n)) return GPE_E_HIP;
+  ctx->case_stale = false;     // (written below, for the active case set)
   if (mode == GPE_MODE_SSE_SEQ) {
     ctx->case_on = 1;
     int rc = run_common(ctx, GPE_MODE_MSE, hi, lo, err, flags);
@@ -2680,6 +2703,7 @@ int gpe_run_cases(gpe_ctx* ctx, int mode, double* out_cases, double* out_hi,
   HIPCHK(hipSetDevice(ctx->device));
   const size_t n = (size_t)ctx->n_prog * (size_t)ctx->n_cases;
   if (ensure(ctx, &ctx->d_case_out, &ctx->case_cap, n)) return GPE_E_HIP;
+  ctx->case_stale = false;     // (written below, for the active case set)
   ctx->case_on = 1;
   int rc = run_common(ctx, mode, ctx->d_hi, ctx->d_lo, ctx->d_err, ctx->d_flags);
   ctx->case_on = 0;
@@ -3018,6 +3042,7 @@ int gpe_run_abserr_cases(gpe_ctx* ctx, double hit_eps, double* out_cases, double
   HIPCHK(hipSetDevice(ctx->device));
   const size_t n = (size_t)ctx->n_prog * (size_t)ctx->n_cases;
   if (ensure(ctx, &ctx->d_case_out, &ctx->case_cap, n)) return GPE_E_HIP;
+  ctx->case_stale = false;     // (written below, for the active case set)
   // whatever way the run is left, the next abs-error run is a plain one
   struct Request {
     gpe_ctx* c;
@@ -3661,7 +3686,7 @@ int gpe_lexicase(gpe_ctx* ctx, const double* values, int64_t n, int64_t n_cases,
     return fail(ctx, GPE_E_INVALID, "lexicase: MT19937 position beyond 624");
   const double* d_val = nullptr;
   if (!values) {                    // the matrix of the last gpe_run_cases
-    if (!ctx->d_case_out || ctx->n_prog <= 0)
+    if (!ctx->d_case_out || ctx->n_prog <= 0 || ctx->case_stale)
       return fail(ctx, GPE_E_STATE, "no per-case values on the device");
     n = ctx->n_prog;
     n_cases = ctx->n_cases;

@@ -161,6 +161,11 @@ def _finish(spec, batch, hi, lo, err, flags):
     return out
 
 
+_NO_SUBSAMPLE = ("%s does not take a case subset: the sharded evaluators' "
+                 "case offsets are global (GPUEvaluator.subsample is "
+                 "single-GPU)")
+
+
 class PopulationSharded(object):
     """Each rank evaluates a length-balanced contiguous slice of the
     population; results are all-gathered (no reduction: bit-identical)."""
@@ -168,6 +173,9 @@ class PopulationSharded(object):
     def __init__(self, local):
         self.local = local
         self.spec = local.spec
+
+    def subsample(self, idx):
+        raise NotImplementedError(_NO_SUBSAMPLE % "PopulationSharded")
 
     def evaluate(self, individuals):
         _check_shardable(self.spec, False)
@@ -282,6 +290,9 @@ class CaseSharded(object):
         self.n_total = n_total
         self.case_offset = case_offset
         self.reduce = reduce
+
+    def subsample(self, idx):
+        raise NotImplementedError(_NO_SUBSAMPLE % "CaseSharded")
 
     def evaluate(self, individuals):
         _check_shardable(self.spec, True)

@@ -24,6 +24,7 @@ exception (``ValueError`` from ``math.sin/cos(inf)``, ``OverflowError`` from
 ``d**2`` or ``fsum``, ``SyntaxError`` for trees over 200 levels, or whatever a
 constant subtree raised).
 """
+import copy
 import math
 import os
 import random
@@ -50,7 +51,7 @@ __all__ = ["SymbRegMSE", "SymbRegNumpySSE", "SymbRegSumSSE",
            "SymbRegScaledMSE", "SymbRegAbsError", "SymbRegCaseErrors",
            "SymbRegCaseAbsErrors",
            "BooleanHits",
-           "exact_dd_sums",
+           "exact_dd_sums", "check_case_subset",
            "TypedBoolHits", "GPUEvaluator", "gpu_map", "pack_bitplanes",
            "unpack_bitplanes", "plan_predict_chunks", "first_error_cases",
            "predict_error"]
@@ -98,6 +99,19 @@ class SymbRegMSE(object):
 
     def upload(self, ctx):
         ctx.set_cases(_lib.GPE_MACHINE_F, self.X, self.terms)
+
+    def subset(self, idx):
+        """The spec of cases *idx* (:meth:`GPUEvaluator.subsample`): a
+        shallow copy with the gathered host arrays and the numbers that
+        depend on them (``n_cases``; :class:`SymbRegScaledMSE`'s ``sy``,
+        ``syy``).  It is never uploaded, and this spec is left as it is."""
+        sub = copy.copy(self)
+        sub.X = np.ascontiguousarray(self.X[:, idx])
+        sub.terms = np.ascontiguousarray(self.terms[:, idx])
+        sub.n_cases = sub.X.shape[1]
+        if getattr(self, "scaled", False):
+            sub.sy, sub.syy = exact_dd_sums(sub.terms[0])
+        return sub
 
     def finish(self, i, hi, lo, err, flags):
         if err != _lib.GPE_NO_ERROR:
@@ -506,6 +520,16 @@ class BooleanHits(object):
     def upload(self, ctx):
         ctx.set_bitplanes(self.planes, self.out_plane, self.n_cases)
 
+    def subset(self, idx):
+        """As :meth:`SymbRegMSE.subset`: the planes of cases *idx*."""
+        sub = copy.copy(self)
+        sub.n_cases = len(idx)
+        sub.planes = pack_bitplanes(
+            unpack_bitplanes(self.planes, self.n_cases)[:, idx])
+        sub.out_plane = pack_bitplanes(
+            unpack_bitplanes(self.out_plane, self.n_cases)[:, idx])[0]
+        return sub
+
     def finish(self, i, hi, lo, err, flags):
         return (int(hi),)
 
@@ -530,6 +554,14 @@ class TypedBoolHits(object):
 
     def upload(self, ctx):
         ctx.set_cases(_lib.GPE_MACHINE_F, self.X, self.labels)
+
+    def subset(self, idx):
+        """As :meth:`SymbRegMSE.subset`: the rows and labels of cases *idx*."""
+        sub = copy.copy(self)
+        sub.X = np.ascontiguousarray(self.X[:, idx])
+        sub.labels = np.ascontiguousarray(self.labels[:, idx])
+        sub.n_cases = sub.X.shape[1]
+        return sub
 
     def finish(self, i, hi, lo, err, flags):
         # (errors only from the exact-integer pass: float(int) overflow)
@@ -570,6 +602,27 @@ class _Rows(object):
         self.X = X
 
 
+def check_case_subset(idx, full_n_cases):
+    """The index vector of :meth:`GPUEvaluator.subsample` as an int64 copy:
+    1-D, at least one entry, integers in ``[0, full_n_cases)`` in any order,
+    duplicates allowed.  ``ValueError`` for an empty, not 1-D or non-integer
+    *idx*; ``IndexError`` naming the first entry out of range (a negative one
+    included: no wrap-around)."""
+    a = np.asarray(idx)
+    if a.ndim != 1:
+        raise ValueError("subsample: idx must be 1-D (got %d-D)" % a.ndim)
+    if a.size == 0:
+        raise ValueError("subsample: idx must name at least one case")
+    if a.dtype.kind not in "iu":
+        raise ValueError("subsample: idx must hold integers (got dtype %s)"
+                         % a.dtype)
+    bad = np.flatnonzero((a < 0) | (a >= full_n_cases))
+    if len(bad):
+        raise IndexError("subsample: idx[%d] = %d is outside [0, %d)"
+                         % (bad[0], a[bad[0]], full_n_cases))
+    return a.astype(np.int64)
+
+
 def _default_device():
     return int(os.environ.get("LOCAL_RANK", "0"))
 
@@ -608,6 +661,13 @@ class GPUEvaluator(object):
         self.ctx = _lib.Context(_default_device() if device is None
                                 else device)
         spec.upload(self.ctx)
+        # case subsampling (subsample): the spec the user passed (never
+        # mutated; self.spec is it, or its subset() while one is active), the
+        # active index vector, and how often case data left the host
+        self._full_spec = spec
+        self.case_subset = None
+        self.full_n_cases = spec.n_cases
+        self.case_uploads = 1
         if precision == "fp32":
             if spec.machine != Machine.F:
                 raise ValueError("fp32 mode applies to the F machine only")
@@ -663,6 +723,49 @@ class GPUEvaluator(object):
             self._predict_ctx = None
             self._predict_X = None
         self.ctx.close()
+
+    @property
+    def n_cases(self):
+        """The active case count (``full_n_cases`` with no subset)."""
+        return self.spec.n_cases
+
+    def subsample(self, idx):
+        """Evaluate on cases *idx* of the resident set from now on, or on the
+        whole set again (*idx* None): down-sampled lexicase, mini-batch
+        fitness, bootstrap resampling.  *idx*: a 1-D integer sequence or
+        array, values in ``[0, full_n_cases)``, any order, duplicates allowed,
+        at least one entry, possibly more than ``full_n_cases``
+        (:func:`check_case_subset`: ``IndexError`` out of range,
+        ``ValueError`` empty, not 1-D or non-integer).
+
+        The rows are gathered on the GPU (``gpe_select_cases``: no case data
+        leaves the host, ``case_uploads`` stays 1).  Afterwards
+        :meth:`evaluate` / :meth:`map`, ``predict(X=None)``,
+        ``predict(scaled=True)``, ``last_scaling``, ``last_mae``,
+        ``last_max_error``, ``last_hits``, :meth:`select_lexicase` and
+        ``tools.selTournamentGPU`` on the resident fitness give what a fresh
+        evaluator built on ``X[:, idx]``, ``terms[:, idx]`` gives — in fp64
+        bit for bit, exceptions included.  A first-error case is a position
+        in *idx* (``case_subset`` maps it back), the MSE / MAE divisor is
+        ``len(idx)``.  ``predict(X=rows)`` is untouched.
+
+        The loaded programs, their exact-int pass and the lowering tables are
+        kept (one population can be run on several subsets without
+        flattening again); the per-case matrix of the last evaluation is
+        dropped, so :meth:`select_lexicase` needs an :meth:`evaluate`
+        first.  The flattener's trig-leaf choice stays the full set's (a
+        column finite on all cases is finite on any subset)."""
+        if idx is None:
+            self.ctx.select_cases(None)
+            self.spec = self._full_spec
+            self.case_subset = None
+        else:
+            idx = check_case_subset(idx, self.full_n_cases)
+            sub = self._full_spec.subset(idx)
+            self.ctx.select_cases(idx)
+            self.spec = sub
+            self.case_subset = idx
+        self._lex_batch = None
 
     # the evaluator is used as toolbox.evaluate
     def __call__(self, individual):

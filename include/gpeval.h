@@ -89,6 +89,27 @@ int gpe_device_info(const gpe_ctx* ctx, int* n_cu, int* clock_khz,
 int gpe_set_cases(gpe_ctx* ctx, int machine, const void* X, int n_vars,
                   int64_t n_cases, const void* terms, int n_terms);
 
+/* Case subsampling: run on rows idx[0..m) of the cases gpe_set_cases uploaded
+ * (down-sampled lexicase, mini-batch fitness, bootstrap resampling) without a
+ * new upload.  idx: values in [0, n_full), any order, duplicates allowed, m
+ * >= 1 may exceed n_full; idx NULL: the full set again.  The rows are
+ * gathered on the device into a second pair of case buffers (grown on need,
+ * reused) and every following run, values run, gpe_lexicase(NULL) and
+ * gpe_tournament(NULL) behaves as after a gpe_set_cases of those rows: case
+ * numbers in first-error words are positions in idx, the MSE divisor is m.
+ * The loaded programs, their exact pass and the lowering tables are kept;
+ * the resident fitness and the per-case matrix are dropped until the next
+ * run.  The column bounds the range pass reads stay the full set's (a hull of
+ * a superset proves every class picked from it, so the handler picked for a
+ * sin/cos may differ from a fresh context's, the bits may not).  idx is
+ * checked on the host before any launch: an entry out of range returns
+ * GPE_E_INVALID with a message naming the first one, and m <= 0 with idx !=
+ * NULL returns GPE_E_INVALID; either leaves the active set as it was.
+ * gpe_set_cases and gpe_set_trig_leaves drop an active subset. */
+int gpe_select_cases(gpe_ctx* ctx, const int64_t* idx, int64_t m);
+/* The active subset's size (m = -1: none active) and the full set's. */
+int gpe_case_subset(const gpe_ctx* ctx, int64_t* m, int64_t* n_full);
+
 /* Population-level evaluation of sin/cos leaves (F machine).  With
  * enable != 0 the context adds 2*n_vars columns, sin(x_v) then cos(x_v),
  * computed on the device at the start of every gpe_run with the same
