@@ -66,6 +66,11 @@ SIGNATURES = {
     "gpe_host_abserr_cases": (_I, [_P, _P, _I64, _I64, _P]),
     "gpe_lexicase": (_I, [_P, _P, _I64, _I64, _P, _I, ctypes.c_double, _P,
                           _I64, _P, ctypes.POINTER(_I64)]),
+    "gpe_run_hit_planes": (_I, [_P, _P, _P, _P, _P]),
+    "gpe_read_hit_planes": (_I, [_P, _P]),
+    "gpe_host_hit_planes": (_I, [_P, _P, _I64, _I64, _P]),
+    "gpe_lexicase_bits": (_I, [_P, _P, _I64, _I64, _P, _I64, _P,
+                               ctypes.POINTER(_I64)]),
     "gpe_set_lowering": (_I, [_P, _I, _I, _P, _I, _P, _I]),
     "gpe_lower_programs": (_I, [_P, _P, _P, _I64, _P, _P, _P, _P, _P]),
     "gpe_lower_begin": (_I, [_P, _I64]),
@@ -241,6 +246,24 @@ def host_abserr_cases(f, terms):
                                       _ptr(out))
     if rc != 0:
         raise GpeError("gpe_host_abserr_cases failed (%d)" % rc)
+    return out
+
+
+def host_hit_planes(result_planes, out_plane, n_cases):
+    """Host twin of a hit-planes run's plane arithmetic (CPU, no GPU): result
+    planes ``uint32[n, ceil(n_cases / 32)]`` against the output plane →
+    hit planes of the same shape (pad bits 0)."""
+    r = np.ascontiguousarray(np.atleast_2d(result_planes), dtype=np.uint32)
+    o = np.ascontiguousarray(out_plane, dtype=np.uint32)
+    units = (int(n_cases) + 31) // 32
+    if n_cases < 1 or r.shape[1] != units or o.shape != (units,):
+        raise ValueError("planes are [n, %d] and the output plane [%d] for "
+                         "%d cases" % (units, units, n_cases))
+    out = np.zeros_like(r)
+    rc = load().gpe_host_hit_planes(_ptr(r), _ptr(o), r.shape[0],
+                                    int(n_cases), _ptr(out))
+    if rc != 0:
+        raise GpeError("gpe_host_hit_planes failed (%d)" % rc)
     return out
 
 
@@ -772,6 +795,60 @@ class Context(object):
                                           _ptr(st), int(k), _ptr(out),
                                           ctypes.byref(failed)),
                     "gpe_lexicase")
+        rng.setstate((version, tuple(int(w) for w in st), gauss))
+        done = int(k) if failed.value < 0 else failed.value
+        return out[:done], failed.value
+
+    def run_hit_planes(self, want_planes=True):
+        """gpe_run_hit_planes → (planes uint32 [n_prog, ceil(n_cases / 32)]
+        or None, hits float64 [n_prog]): a HITS_BITS run that also leaves
+        every program's hit plane on the device (``lexicase_bits(None, ...)``
+        selects on it).  *want_planes* False: no host copy of the matrix is
+        made or allocated."""
+        n = self.n_prog
+        units = (self.n_cases + 31) // 32
+        planes = np.zeros((n, units), dtype=np.uint32) if want_planes \
+            else None
+        hits = np.zeros(n, dtype=np.float64)
+        # (with no programs too: the library then drops its matrix)
+        self._check(self.lib.gpe_run_hit_planes(
+            self.h, _ptr(planes) if want_planes and n else None,
+            _ptr(hits) if n else None, None, None), "gpe_run_hit_planes")
+        return planes, hits
+
+    def hit_planes(self, n):
+        """gpe_read_hit_planes → uint32 [n, ceil(n_cases / 32)]: the bit
+        matrix the last run_hit_planes (of *n* programs) left on the
+        device."""
+        planes = np.zeros((int(n), (self.n_cases + 31) // 32), dtype=np.uint32)
+        self._check(self.lib.gpe_read_hit_planes(self.h, _ptr(planes)),
+                    "gpe_read_hit_planes")
+        return planes
+
+    def lexicase_bits(self, planes, n, n_cases, k, rng):
+        """gpe_lexicase_bits: k lexicase selections on 0/1 values, every case
+        maximised.  *planes*: a program-major hit matrix uint32
+        [n, ceil(n_cases / 32)], or None for the last run_hit_planes' matrix
+        on the device (*n*, *n_cases* are then the context's).  Draws from
+        the ``random.Random``-compatible *rng* as the reference does and
+        advances its state.  Returns (indices, failed) as :meth:`lexicase`."""
+        version, words, gauss = rng.getstate()
+        st = np.asarray(words, dtype=np.uint32)
+        if planes is None:
+            n, n_cases, ptr = 0, 0, None
+        else:
+            units = (int(n_cases) + 31) // 32
+            planes = np.ascontiguousarray(planes, dtype=np.uint32)
+            if planes.shape != (int(n), units):
+                raise ValueError("lexicase_bits: planes must be uint32 "
+                                 "[%d, %d]" % (n, units))
+            ptr = _ptr(planes)
+        out = np.zeros(max(int(k), 1), dtype=np.int32)
+        failed = ctypes.c_int64(-1)
+        self._check(self.lib.gpe_lexicase_bits(self.h, ptr, int(n),
+                                               int(n_cases), _ptr(st), int(k),
+                                               _ptr(out), ctypes.byref(failed)),
+                    "gpe_lexicase_bits")
         rng.setstate((version, tuple(int(w) for w in st), gauss))
         done = int(k) if failed.value < 0 else failed.value
         return out[:done], failed.value

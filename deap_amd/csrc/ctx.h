@@ -487,6 +487,28 @@ struct gpe_ctx {
   int abs_cases = 0;
   double* d_abs = nullptr;
   size_t abs_cap = 0;
+  // A hit-planes run (gpe_run_hit_planes, case_bits.h): a HITS_BITS run whose
+  // kernels (b_eval_hits, b_eval_lanes_hits) also store each program's hit
+  // plane into d_hit, uint32[hit_n][hit_units].  hit_valid: d_hit holds the
+  // matrix of the active case set (gpe_select_cases and gpe_set_cases clear
+  // it).  d_hit_t: the same bits case-major, uint64[32 hit_units][hit_w64]
+  // (program i at bit i % 64 of word i / 64), built by hit_transpose at the
+  // first gpe_lexicase_bits(NULL) after the run (hit_t_valid).  d_lexb_in /
+  // d_lexb_q: a caller's host matrix and its transpose; d_lexb_scratch: the
+  // candidate words and the permutation where they do not fit LDS.
+  int hits_on = 0;
+  uint32_t* d_hit = nullptr;
+  size_t hit_cap = 0;
+  int64_t hit_n = 0, hit_cases = 0, hit_units = 0;
+  bool hit_valid = false, hit_t_valid = false;
+  unsigned long long* d_hit_t = nullptr;
+  size_t hit_t_cap = 0;
+  uint32_t* d_lexb_in = nullptr;
+  size_t lexb_in_cap = 0;
+  unsigned long long* d_lexb_q = nullptr;
+  size_t lexb_q_cap = 0;
+  uint32_t* d_lexb_scratch = nullptr;
+  size_t lexb_scratch_cap = 0;
   char* h_pin_vals = nullptr;        // pinned staging of gpe_run_values' copy back
   size_t h_pin_vals_cap = 0;
   float ms[3] = {0, 0, 0};

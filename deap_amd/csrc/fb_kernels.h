@@ -434,7 +434,10 @@ __device__ __forceinline__ void b_run(const uint32_t* pc, const uint32_t* xs,
 // PLANES (gpe_run_values_bits): each program's result plane, masked to the
 // valid cases, goes to case_out read as uint32[n_prog][n_units]; no popcount,
 // no partials.
-template <int D, bool PLANES>
+// HITS (gpe_run_hit_planes; never with PLANES): the hit count as without it,
+// and each program's hit plane ~(T ^ out) & vmask to case_out in the same
+// layout.
+template <int D, bool PLANES, bool HITS = false>
 __device__ __forceinline__ void b_eval_impl(const Task& a) {
   extern __shared__ uint32_t ldsw[];
   const int lane = threadIdx.x & 63;
@@ -484,7 +487,11 @@ __device__ __forceinline__ void b_eval_impl(const Task& a) {
           ((uint32_t*)a.case_out)[(size_t)prog * a.n_units + wd] = T & vmask;
         continue;
       }
-      uint32_t h = (uint32_t)__builtin_popcount(~(T ^ outp[lane]) & vmask);
+      const uint32_t hit = ~(T ^ outp[lane]) & vmask;
+      if constexpr (HITS) {
+        if (wd < a.n_units) ((uint32_t*)a.case_out)[(size_t)prog * a.n_units + wd] = hit;
+      }
+      uint32_t h = (uint32_t)__builtin_popcount(hit);
       for (int m = 32; m >= 1; m >>= 1) h += __shfl_xor(h, m, 64);
       if (lane == j) acc += (double)h;
     }
@@ -504,6 +511,10 @@ template <int D>
 __global__ __launch_bounds__(kBlock) void b_eval_planes(Task a) {
   b_eval_impl<D, true>(a);
 }
+template <int D>
+__global__ __launch_bounds__(kBlock) void b_eval_hits(Task a) {
+  b_eval_impl<D, false, true>(a);
+}
 
 // Tiny case sets (n_units <= 16 words, e.g. parity-6's 64 cases = 2 words):
 // b_eval would leave 62 of 64 lanes idle, so here each lane interprets its
@@ -512,7 +523,7 @@ __global__ __launch_bounds__(kBlock) void b_eval_planes(Task a) {
 // P) side by side.  Per-lane program counters; the op switch diverges
 // across the wave's programs (they are cost-sorted, so their lengths are
 // close); the words are the same b_run executes.
-template <int D, bool PLANES>
+template <int D, bool PLANES, bool HITS = false>
 __device__ __forceinline__ void b_eval_lanes_impl(const Task& a, int G) {
   extern __shared__ uint32_t ldsw[];
   const int lane = threadIdx.x & 63;
@@ -587,7 +598,12 @@ __device__ __forceinline__ void b_eval_lanes_impl(const Task& a, int G) {
       ((uint32_t*)a.case_out)[(size_t)prog * a.n_units + wd] = T & vmask;
     return;
   }
-  uint32_t h = (uint32_t)__builtin_popcount(~(T ^ outp[wd]) & vmask);
+  const uint32_t hit = ~(T ^ outp[wd]) & vmask;
+  if constexpr (HITS) {
+    if (prog >= 0 && wd < a.n_units)
+      ((uint32_t*)a.case_out)[(size_t)prog * a.n_units + wd] = hit;
+  }
+  uint32_t h = (uint32_t)__builtin_popcount(hit);
   for (int m = G >> 1; m >= 1; m >>= 1) h += __shfl_xor(h, m, 64);
   if (wd == 0 && prog >= 0) {
     double* p = a.part + (size_t)slot * 2;   // one tile group
@@ -603,6 +619,10 @@ __global__ __launch_bounds__(kBlock) void b_eval_lanes(Task a, int G) {
 template <int D>
 __global__ __launch_bounds__(kBlock) void b_eval_lanes_planes(Task a, int G) {
   b_eval_lanes_impl<D, true>(a, G);
+}
+template <int D>
+__global__ __launch_bounds__(kBlock) void b_eval_lanes_hits(Task a, int G) {
+  b_eval_lanes_impl<D, false, true>(a, G);
 }
 
 // Sum partials over tile groups (fixed order) and scatter to program order.

@@ -1829,7 +1829,9 @@ void gpe_destroy(gpe_ctx* ctx) {
                   ctx->masm.d_slot_prog, ctx->masm.d_part, ctx->masm_deep.d_slot_prog,
                   ctx->masm_deep.d_part, ctx->d_jump_a[0], ctx->d_jump_a[1], ctx->d_abs,
                   ctx->aasm.d_slot_prog, ctx->aasm.d_part, ctx->aasm_deep.d_slot_prog,
-                  ctx->aasm_deep.d_part, ctx->d_jump_ac[0], ctx->d_jump_ac[1]};
+                  ctx->aasm_deep.d_part, ctx->d_jump_ac[0], ctx->d_jump_ac[1],
+                  ctx->d_hit, ctx->d_hit_t, ctx->d_lexb_in, ctx->d_lexb_q,
+                  ctx->d_lexb_scratch};
   if (ctx->comm && rccl().ok) (void)rccl().comm_destroy(ctx->comm);
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -1882,6 +1884,7 @@ int gpe_set_cases(gpe_ctx* ctx, int machine, const void* X, int n_vars,
   if (!ctx) return GPE_E_INVALID;
   subset_drop(ctx);            // an active case subset belongs to the old cases
   ctx->last_mode = -1;       // resident fitness no longer matches
+  ctx->hit_valid = false;      // ... nor does the hit-plane matrix
   ctx->n_exact = 0;            // the exact pass belongs to a population
   ctx->ex_all = 0;
   if (machine != GPE_MACHINE_F && machine != GPE_MACHINE_B)
@@ -2810,6 +2813,8 @@ int gpe_run_values_bits(gpe_ctx* ctx, uint32_t* out_planes) {
   if (int rc = run_values(ctx, GPE_MACHINE_B, ctx->d_vals, nullptr)) return rc;
   return values_to_host(ctx, out_planes, ctx->d_vals, words * sizeof(uint32_t));
 }
+
+#include "case_bits.h"
 
 namespace {
 int moments_check(gpe_ctx* ctx) {

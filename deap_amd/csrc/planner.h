@@ -487,18 +487,21 @@ int launch_b(gpe_ctx* ctx, Launch& L, bool deep) {
   a.part = L.d_part;
   const bool planes = ctx->values_on != 0;   // gpe_run_values_bits
   if (planes) a.case_out = (double*)ctx->values_dst;   // uint32[n_prog][n_units]
+  const bool hits = !planes && ctx->hits_on;  // gpe_run_hit_planes
+  if (hits) a.case_out = (double*)ctx->d_hit;          // the same layout
   const size_t lds = lds_bytes(ctx, deep);
   L.lds = lds;
   dim3 grid((unsigned)L.groups, (unsigned)(L.waves / kWaves));
   if (G) {                                   // tiny case sets: lane-packed
-    auto kern = planes ? b_eval_lanes_planes<D> : b_eval_lanes<D>;
+    auto kern = planes ? b_eval_lanes_planes<D>
+                : hits ? b_eval_lanes_hits<D> : b_eval_lanes<D>;
     HIPCHK(hipFuncSetAttribute((const void*)kern,
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, ctx->stream, a, G);
     HIPCHK(hipGetLastError());
     return 0;
   }
-  auto kern = planes ? b_eval_planes<D> : b_eval<D>;
+  auto kern = planes ? b_eval_planes<D> : hits ? b_eval_hits<D> : b_eval<D>;
   HIPCHK(hipFuncSetAttribute((const void*)kern,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, ctx->stream, a);

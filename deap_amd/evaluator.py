@@ -50,7 +50,7 @@ def _tuples1(values, as_int):
 __all__ = ["SymbRegMSE", "SymbRegNumpySSE", "SymbRegSumSSE",
            "SymbRegScaledMSE", "SymbRegAbsError", "SymbRegCaseErrors",
            "SymbRegCaseAbsErrors",
-           "BooleanHits",
+           "BooleanHits", "BooleanCaseHits",
            "exact_dd_sums", "check_case_subset",
            "TypedBoolHits", "GPUEvaluator", "gpu_map", "pack_bitplanes",
            "unpack_bitplanes", "plan_predict_chunks", "first_error_cases",
@@ -537,6 +537,53 @@ class BooleanHits(object):
         return _tuples1(hi, True)
 
 
+class BooleanCaseHits(BooleanHits):
+    """Per-case hits ``int(func(*in_) == out)`` of a boolean problem, for
+    lexicase selection, with :class:`BooleanHits`' count from the same GPU
+    pass (``gpe_run_hit_planes``): one bit per individual and case, stored by
+    the bit-sliced kernels next to the popcount.
+
+    *cases* ``"host"`` (default): an individual's fitness is
+    ``tuple(int(func(*in_) == out) for in_, out in zip(inputs, outputs))``,
+    ``n_cases`` ints 0/1 (weights ``(1.0,) * n_cases``); ``tools.selLexicase``
+    and ``tools.selLexicaseGPU`` select on it unchanged.  ``"device"``: no
+    ``n x n_cases`` matrix is allocated or copied; the fitness is ``(hits,)``
+    as :class:`BooleanHits` gives it and the bit matrix stays on the GPU for
+    :meth:`GPUEvaluator.select_lexicase`.  Either way ``last_hits`` (int64) is
+    filled, :meth:`GPUEvaluator.last_case_hits` reads the matrix back on
+    request and :meth:`GPUEvaluator.select_lexicase` works.  Validation,
+    :meth:`from_rows` and :meth:`subset` are :class:`BooleanHits`'; typed
+    primitive sets (spambase runs on the F machine's typed core) are
+    refused."""
+    hit_planes = True
+
+    def __init__(self, inputs, outputs, cases="host"):
+        BooleanHits.__init__(self, inputs, outputs)
+        if cases not in ("host", "device"):
+            raise ValueError("cases must be 'host' or 'device' (got %r)"
+                             % (cases,))
+        self.cases = cases
+
+    @classmethod
+    def from_rows(cls, inputs, outputs, cases="host"):
+        """Reference layout: ``inputs[case][var]``, ``outputs[case]``."""
+        return cls(np.asarray(inputs).T, np.asarray(outputs), cases)
+
+    def finish(self, i, hi, lo, err, flags, cases=None):
+        if self.cases == "device":
+            return (int(hi),)
+        return tuple(unpack_bitplanes(cases, self.n_cases)[0]
+                     .astype(np.int64).tolist())
+
+    def finish_all(self, hi, lo, err, flags, cases=None):
+        if self.cases == "device":
+            return _tuples1(hi, True)
+        if not len(hi):
+            return []
+        rows = unpack_bitplanes(cases, self.n_cases).astype(np.int64).tolist()
+        return [tuple(row) for row in rows]
+
+
 class TypedBoolHits(object):
     """``(sum(bool(func(*row)) is bool(label) for row, label ...),)``
     (spambase.py:86) evaluated on every row."""
@@ -646,6 +693,15 @@ class GPUEvaluator(object):
         for throughput, with the agreement DESIGN.md §4 states."""
         if precision not in ("fp64", "fp32"):
             raise ValueError("precision must be 'fp64' or 'fp32'")
+        if getattr(spec, "hit_planes", False):
+            for p in (pset if isinstance(pset, (list, tuple)) else [pset]):
+                if getattr(p, "ret", object) is not object:
+                    raise NotImplementedError(
+                        "%s does not take a typed primitive set (%s returns "
+                        "%r): typed programs run on the F machine's typed "
+                        "core, which stores no hit planes"
+                        % (type(spec).__name__, getattr(p, "name", "pset"),
+                           p.ret))
         self.pset = pset
         self.spec = spec
         self.precision = precision
@@ -1015,6 +1071,12 @@ class GPUEvaluator(object):
             lo = np.zeros(len(err))
             self.last_mae, self.last_max_error, self.last_hits = \
                 self.spec.figures(hi, err, flags)
+        elif getattr(self.spec, "hit_planes", False):
+            # (the hit planes in cases' place; the counts alone come back)
+            cases, hi = self.ctx.run_hit_planes(
+                want_planes=self.spec.cases == "host")
+            lo = err = flags = None
+            self.last_hits = np.asarray(hi).astype(np.int64)
         elif getattr(self.spec, "per_case", False):
             cases, hi, lo, err, flags = self.ctx.run_cases(
                 self.spec.mode, self.spec.n_cases)
@@ -1051,7 +1113,8 @@ class GPUEvaluator(object):
         self.stats["individuals"] += len(individuals)
         self.stats["node_evals"] += batch.n_nodes() * \
             self.spec.n_cases
-        abs_cases = getattr(self.spec, "abs_cases", False)
+        abs_cases = getattr(self.spec, "abs_cases", False) or \
+            getattr(self.spec, "hit_planes", False)
         if (cases is None or abs_cases) and hasattr(self.spec, "finish_all"):
             args = [None if x is None else np.asarray(x)
                     for x in (hi, lo, err, flags)]
@@ -1099,16 +1162,41 @@ class GPUEvaluator(object):
         individual of the batch raised, its exception is raised here, the
         first in order.  The device selection's limits (16,384 individuals
         for ``"automatic"``; ``n/32 + n_cases`` words within 48 KiB of LDS)
-        are raised as the library words them."""
+        are raised as the library words them.
+
+        After a :class:`BooleanCaseHits` evaluation the values are 0/1 hits
+        and every case is maximised.  On such values ``selLexicase``,
+        ``selEpsilonLexicase`` with ``0 <= epsilon < 1`` and
+        ``selAutomaticEpsilonLexicase`` select the same individuals with the
+        same draws and leave the same ``random`` state: a case keeps the
+        candidates that hit it when some do and everybody otherwise, whatever
+        an epsilon below 1 subtracts, and a 0/1 sample's median absolute
+        deviation is 0 or 0.5.  All three modes therefore run one bit kernel
+        (``gpe_lexicase_bits``), which has neither of the limits above.
+        ``epsilon >= 1`` raises ``ValueError``: past 1 every candidate
+        survives every case and the selection is ``random.choice``; a
+        negative epsilon raises too."""
         if mode not in self.LEXICASE_MODES:
             raise ValueError("mode must be 'plain', 'epsilon' or 'automatic' "
                              "(got %r)" % (mode,))
         individuals = list(individuals)
+        bits = getattr(self.spec, "hit_planes", False)
+        if bits and mode == "epsilon":
+            if not 0.0 <= epsilon < 1.0:      # (a nan is refused as well)
+                raise ValueError(
+                    "select_lexicase: epsilon must be in [0, 1) on 0/1 hits "
+                    "(got %r): %s" % (epsilon,
+                                      "a negative epsilon leaves a case no "
+                                      "candidate" if epsilon < 0 else
+                                      "from 1 on every candidate survives "
+                                      "every case and the selection is "
+                                      "random.choice(individuals)"))
         if self._lex_batch is None:
             raise ValueError(
                 "select_lexicase: this evaluator's last evaluate / map left "
                 "no per-case matrix on the GPU (its spec is %s; evaluate "
-                "with SymbRegCaseAbsErrors or SymbRegCaseErrors first)"
+                "with SymbRegCaseAbsErrors, SymbRegCaseErrors or "
+                "BooleanCaseHits first)"
                 % type(self.spec).__name__)
         last, results = self._lex_batch
         if len(individuals) != len(last) or \
@@ -1129,12 +1217,31 @@ class GPUEvaluator(object):
             return []
         if not individuals:               # individuals[0] in the reference
             raise IndexError("list index out of range")
-        idx, failed = self.ctx.lexicase(
-            None, np.zeros(self.spec.n_cases, dtype=np.uint8), k,
-            random._inst, self.LEXICASE_MODES[mode], epsilon)
+        if bits:
+            idx, failed = self.ctx.lexicase_bits(None, 0, 0, k, random._inst)
+        else:
+            idx, failed = self.ctx.lexicase(
+                None, np.zeros(self.spec.n_cases, dtype=np.uint8), k,
+                random._inst, self.LEXICASE_MODES[mode], epsilon)
         if failed >= 0:                   # random.choice([]) in the reference
             raise IndexError("Cannot choose from an empty sequence")
         return [individuals[i] for i in idx.tolist()]
+
+    def last_case_hits(self):
+        """``bool[n, n_cases]``: the hit matrix of the last
+        :class:`BooleanCaseHits` evaluation, read back from the device's bit
+        matrix on request (either *cases* mode).  ``ValueError`` when the
+        last evaluate / map left none (as :meth:`select_lexicase`)."""
+        if not getattr(self.spec, "hit_planes", False) or \
+                self._lex_batch is None:
+            raise ValueError(
+                "last_case_hits: this evaluator's last evaluate / map left "
+                "no hit planes on the GPU (its spec is %s; evaluate with "
+                "BooleanCaseHits first)" % type(self.spec).__name__)
+        n = len(self._lex_batch[0])
+        if n == 0:
+            return np.zeros((0, self.spec.n_cases), dtype=bool)
+        return unpack_bitplanes(self.ctx.hit_planes(n), self.spec.n_cases)
 
     def map(self, individuals):
         return _yield_until_error(self.evaluate(list(individuals)))

@@ -311,6 +311,54 @@ int gpe_lexicase(gpe_ctx* ctx, const double* values, int64_t n,
                  double epsilon, uint32_t* mt_state, int64_t k, int32_t* out,
                  int64_t* failed);
 
+/* A hit-planes run (B machine): gpe_run in GPE_MODE_HITS_BITS in every
+ * respect — the same hit counts bit for bit in out_hi, the same resident
+ * fitness for gpe_tournament(NULL), the same launch plans — whose kernels, in
+ * the same pass, also store each program's hit plane ~(T ^ out) & vmask into a
+ * context-owned device matrix uint32[n_prog][ceil(n_cases / 32)]: bit c % 32
+ * of word c / 32 is 1 where the program's output equals the case's, the bits
+ * past n_cases are 0.  out_planes: the HOST copy uint32[n_prog][n_units]
+ * (through pinned staging), or NULL to leave the matrix on the device only,
+ * where gpe_lexicase_bits(ctx, NULL, ...) selects on it.  out_hi, out_err,
+ * out_flags (any may be NULL): gpe_run's.  The F machine gets GPE_E_ARG.
+ * Residency: a hit-planes run replaces the bit matrix; gpe_select_cases and
+ * gpe_set_cases drop it; gpe_run, gpe_run_values_bits and loading programs
+ * leave it as it is (gpe_lexicase_bits(NULL) refuses while the loaded program
+ * count differs from the matrix's).
+ * Replaces: tuple(int(func(*in_) == out) for in_, out in zip(inputs,
+ * outputs)) per individual (multiplexer.py:75 / parity.py:68 before the sum),
+ * the per-case fitness lexicase selection reads. */
+int gpe_run_hit_planes(gpe_ctx* ctx, uint32_t* out_planes, double* out_hi,
+                       uint64_t* out_err, uint32_t* out_flags);
+
+/* The resident bit matrix of the last gpe_run_hit_planes into the HOST array
+ * out_planes uint32[n_prog][n_units]; GPE_E_STATE when none is resident. */
+int gpe_read_hit_planes(gpe_ctx* ctx, uint32_t* out_planes);
+
+/* Host twin of the plane arithmetic (no GPU): out[n][n_units] =
+ * ~(result_planes[n][n_units] ^ out_plane[n_units]) with the bits past
+ * n_cases of the last word cleared. */
+int gpe_host_hit_planes(const uint32_t* result_planes, const uint32_t* out_plane,
+                        int64_t n, int64_t n_cases, uint32_t* out);
+
+/* Device lexicase selection on 0/1 per-case values, every case maximised,
+ * replaying the reference's random stream as gpe_lexicase does.  On such
+ * values selLexicase, selEpsilonLexicase with 0 <= epsilon < 1 and
+ * selAutomaticEpsilonLexicase (deap/tools/selection.py:214-320) make the same
+ * draws and pick the same individuals (a 0/1 sample's median absolute
+ * deviation is 0 or 0.5), so there is no mode.  planes is a HOST program-major
+ * hit matrix uint32[n][ceil(n_cases / 32)] (pad bits 0), or NULL to select on
+ * the matrix of the last gpe_run_hit_planes (n = programs) without a host
+ * round trip.  The matrix is transposed on the device into case-major 64-bit
+ * planes (once per hit-planes run); a case keeps cand & plane[c] when that is
+ * not empty, else every candidate.  Candidate words and the case permutation
+ * live in LDS while ceil(n / 32) + n_cases words fit 48 KiB, else in device
+ * scratch: no population or case limit beyond memory.  mt_state, out and
+ * failed are gpe_lexicase's; *failed can only be set for n = 0. */
+int gpe_lexicase_bits(gpe_ctx* ctx, const uint32_t* planes, int64_t n,
+                      int64_t n_cases, uint32_t* mt_state, int64_t k,
+                      int32_t* out, int64_t* failed);
+
 /* Device tournament selection that replays the reference's random stream:
  * selTournament (deap/tools/selection.py:51-69, aspirants drawn by selRandom
  * :15-28, i.e. random.choice) — k tournaments of tournsize aspirants, the
