@@ -71,6 +71,11 @@ SIGNATURES = {
     "gpe_host_hit_planes": (_I, [_P, _P, _I64, _I64, _P]),
     "gpe_lexicase_bits": (_I, [_P, _P, _I64, _I64, _P, _I64, _P,
                                ctypes.POINTER(_I64)]),
+    "gpe_informed_cases": (_I, [_P, _P, _I64, _I64, ctypes.c_double,
+                                ctypes.c_uint64, _I64, _P, _P]),
+    "gpe_host_informed_cases": (_I, [_P, _I64, _I64, ctypes.c_uint64, _I64,
+                                     _P, _P]),
+    "gpe_host_hit_threshold": (_I, [_P, _I64, _I64, ctypes.c_double, _P]),
     "gpe_set_lowering": (_I, [_P, _I, _I, _P, _I, _P, _I]),
     "gpe_lower_programs": (_I, [_P, _P, _P, _I64, _P, _P, _P, _P, _P]),
     "gpe_lower_begin": (_I, [_P, _I64]),
@@ -264,6 +269,44 @@ def host_hit_planes(result_planes, out_plane, n_cases):
                                     int(n_cases), _ptr(out))
     if rc != 0:
         raise GpeError("gpe_host_hit_planes failed (%d)" % rc)
+    return out
+
+
+def _check_planes(what, planes, n_cases):
+    units = (int(n_cases) + 31) // 32
+    planes = np.ascontiguousarray(planes, dtype=np.uint32)
+    if n_cases < 1 or planes.ndim != 2 or planes.shape[1] != units:
+        raise ValueError("%s: planes must be uint32 [n, %d] for %d cases"
+                         % (what, units, n_cases))
+    return planes
+
+
+def host_informed_cases(planes, n_cases, seed, m):
+    """Host twin of :meth:`Context.informed_cases` (CPU, no GPU): the
+    farthest-first subset of *m* cases of a program-major hit matrix
+    ``uint32[n, ceil(n_cases / 32)]`` → ``(idx int64[m], dist int32[m])``."""
+    planes = _check_planes("host_informed_cases", planes, n_cases)
+    idx = np.zeros(max(int(m), 1), dtype=np.int64)
+    dist = np.zeros(max(int(m), 1), dtype=np.int32)
+    rc = load().gpe_host_informed_cases(
+        _ptr(planes), planes.shape[0], int(n_cases),
+        int(seed) & 0xFFFFFFFFFFFFFFFF, int(m), _ptr(idx), _ptr(dist))
+    if rc != 0:
+        raise GpeError("gpe_host_informed_cases failed (%d)" % rc)
+    return idx[:int(m)], dist[:int(m)]
+
+
+def host_hit_threshold(cases, eps):
+    """Host twin of the thresholding ``gpe_informed_cases`` applies to the F
+    machine's per-case matrix (CPU, no GPU): ``cases[n, n_cases]`` float64 →
+    hit planes ``uint32[n, ceil(n_cases / 32)]``, a bit set where the value is
+    finite and ``<= eps``."""
+    e = np.ascontiguousarray(np.atleast_2d(cases), dtype=np.float64)
+    out = np.zeros((e.shape[0], (e.shape[1] + 31) // 32), dtype=np.uint32)
+    rc = load().gpe_host_hit_threshold(_ptr(e), e.shape[0], e.shape[1],
+                                       float(eps), _ptr(out))
+    if rc != 0:
+        raise GpeError("gpe_host_hit_threshold failed (%d)" % rc)
     return out
 
 
@@ -852,6 +895,32 @@ class Context(object):
         rng.setstate((version, tuple(int(w) for w in st), gauss))
         done = int(k) if failed.value < 0 else failed.value
         return out[:done], failed.value
+
+    def informed_cases(self, planes, n, n_cases, eps, seed, m):
+        """gpe_informed_cases: the farthest-first subset of *m* cases
+        (informed down-sampling) → ``(idx int64[m], dist int32[m])``: the
+        cases in pick order and each pick's Hamming distance to the nearest
+        case picked before it (``dist[0] == -1``).  *planes*: a program-major
+        hit matrix uint32 [n, ceil(n_cases / 32)], or None for the resident
+        matrix of the loaded programs (*n*, *n_cases* are then the
+        context's): the last run_hit_planes' on the B machine, the last
+        run_abserr_cases' thresholded at *eps* on the F machine.  *seed*: the
+        64-bit seed of the tie-break keys.  Nothing resident is disturbed."""
+        if planes is None:
+            n, n_cases, ptr = 0, 0, None
+        else:
+            planes = _check_planes("informed_cases", planes, n_cases)
+            if planes.shape[0] != int(n):
+                raise ValueError("informed_cases: planes must be uint32 "
+                                 "[%d, %d]" % (n, planes.shape[1]))
+            ptr = _ptr(planes)
+        idx = np.zeros(max(int(m), 1), dtype=np.int64)
+        dist = np.zeros(max(int(m), 1), dtype=np.int32)
+        self._check(self.lib.gpe_informed_cases(
+            self.h, ptr, int(n), int(n_cases), float(eps),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(m), _ptr(idx), _ptr(dist)),
+            "gpe_informed_cases")
+        return idx[:int(m)], dist[:int(m)]
 
     def set_lowering(self, machine, nv, leaf, entries, n_entries):
         """gpe_set_lowering: the pset tables of device lowering (``leaf``

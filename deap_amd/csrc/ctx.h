@@ -234,6 +234,9 @@ struct gpe_ctx {
   // d_case_out holds no matrix of the current case set (a subset was selected
   // or dropped since the run that wrote it): gpe_lexicase(NULL) refuses
   bool case_stale = false;
+  // programs of the run that wrote d_case_out (its rows): gpe_informed_cases
+  // (NULL) refuses while another count is loaded
+  int64_t case_n = 0;
   // programs (flattener format)
   uint32_t* d_code = nullptr;
   size_t code_cap = 0;
@@ -509,6 +512,25 @@ struct gpe_ctx {
   size_t lexb_q_cap = 0;
   uint32_t* d_lexb_scratch = nullptr;
   size_t lexb_scratch_cap = 0;
+  // Informed down-sampling (gpe_informed_cases, case_informed.h).  d_inf_hit /
+  // d_inf_q: the F machine's per-case matrix thresholded into hit planes
+  // uint32[n][n_units] and their case-major transpose — scratch of the call,
+  // never d_hit / d_hit_t (hit_valid is the B machine's).  d_inf_mind: each
+  // case's distance to its nearest chosen case (-1: chosen); d_inf_part: two
+  // sets of block partials (key, mind << 32 | case), written by one launch and
+  // reduced by the next; d_inf_idx / d_inf_dist: the picks.
+  uint32_t* d_inf_hit = nullptr;
+  size_t inf_hit_cap = 0;
+  unsigned long long* d_inf_q = nullptr;
+  size_t inf_q_cap = 0;
+  int32_t* d_inf_mind = nullptr;
+  size_t inf_mind_cap = 0;
+  unsigned long long* d_inf_part = nullptr;
+  size_t inf_part_cap = 0;
+  int64_t* d_inf_idx = nullptr;
+  size_t inf_idx_cap = 0;
+  int32_t* d_inf_dist = nullptr;
+  size_t inf_dist_cap = 0;
   char* h_pin_vals = nullptr;        // pinned staging of gpe_run_values' copy back
   size_t h_pin_vals_cap = 0;
   float ms[3] = {0, 0, 0};

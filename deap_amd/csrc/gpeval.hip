@@ -1831,7 +1831,8 @@ void gpe_destroy(gpe_ctx* ctx) {
                   ctx->aasm.d_slot_prog, ctx->aasm.d_part, ctx->aasm_deep.d_slot_prog,
                   ctx->aasm_deep.d_part, ctx->d_jump_ac[0], ctx->d_jump_ac[1],
                   ctx->d_hit, ctx->d_hit_t, ctx->d_lexb_in, ctx->d_lexb_q,
-                  ctx->d_lexb_scratch};
+                  ctx->d_lexb_scratch, ctx->d_inf_hit, ctx->d_inf_q, ctx->d_inf_mind,
+                  ctx->d_inf_part, ctx->d_inf_idx, ctx->d_inf_dist};
   if (ctx->comm && rccl().ok) (void)rccl().comm_destroy(ctx->comm);
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -2555,6 +2556,7 @@ int run_numpy(gpe_ctx* ctx, int mode, double* hi, double* lo,
   const size_t n = (size_t)ctx->n_prog * (size_t)ctx->n_cases;
   if (ensure(ctx, &ctx->d_case_out, &ctx->case_cap, n)) return GPE_E_HIP;
   ctx->case_stale = false;     // (written below, for the active case set)
+  ctx->case_n = ctx->n_prog;   // ... by the loaded programs (gpe_informed_cases checks)
   if (mode == GPE_MODE_SSE_SEQ) {
     ctx->case_on = 1;
     int rc = run_common(ctx, GPE_MODE_MSE, hi, lo, err, flags);
@@ -2707,6 +2709,7 @@ int gpe_run_cases(gpe_ctx* ctx, int mode, double* out_cases, double* out_hi,
   const size_t n = (size_t)ctx->n_prog * (size_t)ctx->n_cases;
   if (ensure(ctx, &ctx->d_case_out, &ctx->case_cap, n)) return GPE_E_HIP;
   ctx->case_stale = false;     // (written below, for the active case set)
+  ctx->case_n = ctx->n_prog;   // ... by the loaded programs (gpe_informed_cases checks)
   ctx->case_on = 1;
   int rc = run_common(ctx, mode, ctx->d_hi, ctx->d_lo, ctx->d_err, ctx->d_flags);
   ctx->case_on = 0;
@@ -2815,6 +2818,7 @@ int gpe_run_values_bits(gpe_ctx* ctx, uint32_t* out_planes) {
 }
 
 #include "case_bits.h"
+#include "case_informed.h"
 
 namespace {
 int moments_check(gpe_ctx* ctx) {
@@ -3048,6 +3052,7 @@ int gpe_run_abserr_cases(gpe_ctx* ctx, double hit_eps, double* out_cases, double
   const size_t n = (size_t)ctx->n_prog * (size_t)ctx->n_cases;
   if (ensure(ctx, &ctx->d_case_out, &ctx->case_cap, n)) return GPE_E_HIP;
   ctx->case_stale = false;     // (written below, for the active case set)
+  ctx->case_n = ctx->n_prog;   // ... by the loaded programs (gpe_informed_cases checks)
   // whatever way the run is left, the next abs-error run is a plain one
   struct Request {
     gpe_ctx* c;

@@ -182,6 +182,9 @@ class PopulationSharded(object):
     def subsample(self, idx):
         raise NotImplementedError(_NO_SUBSAMPLE % "PopulationSharded")
 
+    def informed_subsample(self, m, eps=None, apply=True):
+        raise NotImplementedError(_NO_SUBSAMPLE % "PopulationSharded")
+
     def evaluate(self, individuals):
         _check_shardable(self.spec, False)
         torch, dist, dev = _torch_dist(self.local)
@@ -297,6 +300,9 @@ class CaseSharded(object):
         self.reduce = reduce
 
     def subsample(self, idx):
+        raise NotImplementedError(_NO_SUBSAMPLE % "CaseSharded")
+
+    def informed_subsample(self, m, eps=None, apply=True):
         raise NotImplementedError(_NO_SUBSAMPLE % "CaseSharded")
 
     def evaluate(self, individuals):

@@ -771,6 +771,8 @@ class GPUEvaluator(object):
         # stay theirs) and results of the last evaluation that left a
         # per-case matrix on the GPU
         self._lex_batch = None
+        # informed_subsample: each pick's distance to the nearest earlier one
+        self.last_informed_distances = np.zeros(0, dtype=np.int32)
 
     def close(self):
         """Release the device contexts (the evaluator's and predict's)."""
@@ -822,6 +824,80 @@ class GPUEvaluator(object):
             self.spec = sub
             self.case_subset = idx
         self._lex_batch = None
+
+    def informed_subsample(self, m, eps=None, apply=True):
+        """Informed down-sampling (Boldi et al. 2023): choose *m* cases by a
+        farthest-first traversal of the per-case matrix the last
+        :meth:`evaluate` / :meth:`map` left on the GPU, and (with *apply*)
+        :meth:`subsample` to them.  Returns the cases, ``int64[m]`` in pick
+        order, no duplicates.
+
+        Evaluate a sample of the parents on all cases first
+        (``subsample(None)``; :class:`BooleanCaseHits` or
+        :class:`SymbRegCaseAbsErrors`, either *cases* mode).  Two cases are as
+        far apart as the number of those individuals that pass one and fail
+        the other; for the regression spec a case is passed when its absolute
+        error is finite and ``<= eps`` (default ``spec.hit_eps``; *eps* with
+        :class:`BooleanCaseHits` is a ``ValueError``).  The first case is
+        drawn at random, every further one is the case farthest from all
+        chosen so far, so cases that the same individuals solve stop crowding
+        the subset; once only duplicates of chosen cases remain, they follow
+        in random order.  The exact rule, with its SplitMix64 tie-break keys,
+        is ``gpe_informed_cases``' (include/gpeval.h); no ``n x n_cases`` copy
+        leaves the GPU.
+
+        ``seed = random.getrandbits(64)`` is the only draw from the module
+        ``random`` stream.  ``last_informed_distances`` (int32 ``[m]``) holds
+        each pick's distance to the nearest case picked before it (-1 for the
+        first).  *apply* False changes nothing else: the per-case matrix still
+        serves :meth:`select_lexicase`.  ``ValueError``: no per-case matrix of
+        the full case set (or :class:`SymbRegCaseErrors`' squared errors), *m*
+        outside ``[1, full_n_cases]``.  If an individual of the batch raised,
+        its exception is raised here, the first in order."""
+        name = type(self.spec).__name__
+        bits = getattr(self.spec, "hit_planes", False)
+        if self._lex_batch is None or self.case_subset is not None or \
+                not (bits or getattr(self.spec, "abs_cases", False)):
+            raise ValueError(
+                "informed_subsample: it needs the per-case matrix of a "
+                "BooleanCaseHits or SymbRegCaseAbsErrors evaluation on the "
+                "full case set (the spec is %s, %s, %s): subsample(None) and "
+                "evaluate the parent sample first"
+                % (name, "no per-case matrix is on the GPU"
+                   if self._lex_batch is None else "a per-case matrix is on "
+                   "the GPU", "no case subset is active"
+                   if self.case_subset is None else "a case subset is active"))
+        if bits and eps is not None:
+            raise ValueError("informed_subsample: eps applies to "
+                             "SymbRegCaseAbsErrors; BooleanCaseHits' cases "
+                             "are hits already (got eps=%r)" % (eps,))
+        if not 1 <= m <= self.full_n_cases:
+            raise ValueError("informed_subsample: m must be in [1, %d] (got "
+                             "%r)" % (self.full_n_cases, m))
+        last, results = self._lex_batch
+        if self.ctx.n_prog != len(last):
+            raise ValueError(
+                "informed_subsample: the context now holds %d programs, not "
+                "the %d of the last evaluate / map; evaluate the batch again"
+                % (self.ctx.n_prog, len(last)))
+        for res in results:
+            if isinstance(res, BaseException):
+                raise res
+        if not last:
+            raise ValueError("informed_subsample: the last evaluate / map "
+                             "held no individuals")
+        if not bits:
+            eps = self.spec.hit_eps if eps is None else float(eps)
+            if not eps >= 0.0:
+                raise ValueError("informed_subsample: eps must be >= 0 (got "
+                                 "%r)" % (eps,))
+        seed = random.getrandbits(64)
+        idx, dist = self.ctx.informed_cases(None, 0, 0, 0.0 if bits else eps,
+                                            seed, int(m))
+        self.last_informed_distances = dist
+        if apply:
+            self.subsample(idx)
+        return idx
 
     # the evaluator is used as toolbox.evaluate
     def __call__(self, individual):

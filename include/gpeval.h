@@ -359,6 +359,51 @@ int gpe_lexicase_bits(gpe_ctx* ctx, const uint32_t* planes, int64_t n,
                       int64_t n_cases, uint32_t* mt_state, int64_t k,
                       int32_t* out, int64_t* failed);
 
+/* Informed down-sampling (Boldi et al. 2023): a farthest-first subset of m
+ * cases from a 0/1 per-case matrix hit[n][n_cases].  The distance of two cases
+ * is the Hamming distance of their columns.  key[c] is the (c + 1)-th output
+ * of SplitMix64 seeded with `seed`:
+ *   z = seed + (c + 1) * 0x9E3779B97F4A7C15;
+ *   z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *   z = (z ^ z >> 27) * 0x94D049BB133111EB;   key = z ^ z >> 31   (mod 2^64)
+ * and the cases are totally ordered by (key[c], c).  out_idx[0] is the
+ * smallest case in that order and out_dist[0] = -1; mind[c] is the distance
+ * of case c to out_idx[0].  Pick t = 1 .. m - 1 is the unchosen case with the
+ * largest mind, ties to the smallest (key, c); out_dist[t] is its mind, and
+ * mind[c] = min(mind[c], distance(c, out_idx[t])) afterwards.  out_idx
+ * int64[m] has no duplicates; out_dist int32[m] is non-increasing from index
+ * 1 on.  Once every remaining mind is 0 the rest arrive in key order.
+ * planes is a HOST program-major hit matrix uint32[n][ceil(n_cases / 32)] (pad
+ * bits 0), as gpe_lexicase_bits takes it (eps is ignored), or NULL for the
+ * resident matrix of the loaded programs (n, n_cases are then the context's):
+ * on the B machine the hit planes of the last gpe_run_hit_planes; on the F
+ * machine the per-case matrix of the last gpe_run_abserr_cases /
+ * gpe_run_cases, where case c is a hit of program i when its value e is finite
+ * and e <= eps (a nan or inf is never a hit, also with eps = inf: the rule of
+ * gpe_run_abserr's hit count; eps >= 0 and not nan, else GPE_E_ARG).
+ * GPE_E_STATE when no such matrix of the active case set is resident (after
+ * gpe_select_cases, before a per-case run, or while the loaded program count
+ * differs from that run's).  GPE_E_INVALID with a message
+ * naming the value for m < 1, m > n_cases, n < 1 or n > INT32_MAX.  One launch
+ * per pick, no grid-wide barrier.  The call selects nothing: the resident
+ * fitness, the per-case matrix, the hit planes (the thresholded planes have
+ * buffers of their own) and the active case set are not disturbed. */
+int gpe_informed_cases(gpe_ctx* ctx, const uint32_t* planes, int64_t n,
+                       int64_t n_cases, double eps, uint64_t seed, int64_t m,
+                       int64_t* out_idx, int32_t* out_dist);
+
+/* Host twin of gpe_informed_cases on a host matrix (no GPU): the same
+ * arithmetic in plain C++. */
+int gpe_host_informed_cases(const uint32_t* planes, int64_t n, int64_t n_cases,
+                            uint64_t seed, int64_t m, int64_t* out_idx,
+                            int32_t* out_dist);
+
+/* Host twin of the F machine's thresholding (no GPU): cases double[n][n_cases]
+ * into hit planes out_planes uint32[n][ceil(n_cases / 32)], bit c % 32 of word
+ * c / 32 set where the value is finite and <= eps, pad bits 0. */
+int gpe_host_hit_threshold(const double* cases, int64_t n, int64_t n_cases,
+                           double eps, uint32_t* out_planes);
+
 /* Device tournament selection that replays the reference's random stream:
  * selTournament (deap/tools/selection.py:51-69, aspirants drawn by selRandom
  * :15-28, i.e. random.choice) — k tournaments of tournsize aspirants, the
