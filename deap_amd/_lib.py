@@ -76,6 +76,13 @@ SIGNATURES = {
     "gpe_host_informed_cases": (_I, [_P, _I64, _I64, ctypes.c_uint64, _I64,
                                      _P, _P]),
     "gpe_host_hit_threshold": (_I, [_P, _I64, _I64, ctypes.c_double, _P]),
+    "gpe_lexicase_par": (_I, [_P, _P, _I64, _I64, _P, _I, ctypes.c_double,
+                              ctypes.c_uint64, _I64, _P, _P]),
+    "gpe_lexicase_bits_par": (_I, [_P, _P, _I64, _I64, ctypes.c_uint64, _I64,
+                                   _P, _P]),
+    "gpe_host_lexicase_par": (_I, [_P, _I64, _I64, _P, _I, ctypes.c_double,
+                                   ctypes.c_uint64, _I64, _P, _P]),
+    "gpe_lexicase_par_lds_values": (_I64, []),
     "gpe_set_lowering": (_I, [_P, _I, _I, _P, _I, _P, _I]),
     "gpe_lower_programs": (_I, [_P, _P, _P, _I64, _P, _P, _P, _P, _P]),
     "gpe_lower_begin": (_I, [_P, _I64]),
@@ -308,6 +315,53 @@ def host_hit_threshold(cases, eps):
     if rc != 0:
         raise GpeError("gpe_host_hit_threshold failed (%d)" % rc)
     return out
+
+
+def lexicase_par_lds_values():
+    """The number of compacted candidate values a ``gpe_lexicase_par`` block
+    keeps in LDS (larger candidate sets go through device scratch)."""
+    return int(load().gpe_lexicase_par_lds_values())
+
+
+def _check_lexicase_par(what, n, n_cases, k, mode):
+    if n < 1 or n > 2 ** 31 - 1:
+        raise ValueError("%s: n = %d individuals (need 1 .. 2^31 - 1)"
+                         % (what, n))
+    if n_cases < 1 or n_cases > 2 ** 31 - 1:
+        raise ValueError("%s: n_cases = %d (need 1 .. 2^31 - 1)"
+                         % (what, n_cases))
+    if k < 0:
+        raise ValueError("%s: k = %d selections (need >= 0)" % (what, k))
+    if mode not in (0, 1, 2):
+        raise ValueError("%s: mode must be 0, 1 or 2 (got %r)" % (what, mode))
+
+
+def host_lexicase_par(values, maximise, k, seed, mode=0, epsilon=0.0):
+    """Host twin of :meth:`Context.lexicase_par` (CPU, no GPU): the rule of
+    ``gpe_lexicase_par`` in plain C++ on ``values`` [n, n_cases] →
+    ``(indices int32[k], failed)``: -1 where a selection ended with no
+    candidate, *failed* the first such selection or -1.  ``ValueError`` for
+    what the library refuses: an empty matrix, ``k < 0``, a mode outside
+    0..2, a *maximise* of another length."""
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    if values.ndim != 2:
+        raise ValueError("host_lexicase_par: values must be [n, n_cases] "
+                         "(got %d dimensions)" % values.ndim)
+    n, c = values.shape
+    k, mode = int(k), int(mode)
+    _check_lexicase_par("host_lexicase_par", n, c, k, mode)
+    maximise = np.ascontiguousarray(maximise, dtype=np.uint8)
+    if maximise.shape != (c,):
+        raise ValueError("host_lexicase_par: maximise must have one entry per "
+                         "case (%d), got shape %r" % (c, maximise.shape))
+    out = np.zeros(max(k, 1), dtype=np.int32)
+    failed = ctypes.c_int64(-1)
+    rc = load().gpe_host_lexicase_par(
+        _ptr(values), n, c, _ptr(maximise), mode, float(epsilon),
+        int(seed) & 0xFFFFFFFFFFFFFFFF, k, _ptr(out), ctypes.byref(failed))
+    if rc != 0:
+        raise GpeError("gpe_host_lexicase_par failed (%d)" % rc)
+    return out[:k], failed.value
 
 
 TRIG_CLASSES = ("general", "mid", "small")
@@ -895,6 +949,52 @@ class Context(object):
         rng.setstate((version, tuple(int(w) for w in st), gauss))
         done = int(k) if failed.value < 0 else failed.value
         return out[:done], failed.value
+
+    def lexicase_par(self, values, maximise, k, seed, mode=0, epsilon=0.0):
+        """gpe_lexicase_par: k independent selections on ``values``
+        [n, n_cases] (None: the last run_cases / run_abserr_cases matrix), one
+        workgroup each; case orders and choices are SplitMix64 keys of the
+        64-bit *seed* (the rule: include/gpeval.h), no ``random`` draw is
+        made.  Returns (indices int32[k], failed): -1 where a selection ended
+        with no candidate, *failed* the first such selection or -1."""
+        maximise = np.ascontiguousarray(maximise, dtype=np.uint8)
+        if values is None:
+            n, c, ptr = 0, len(maximise), None
+        else:
+            values = np.ascontiguousarray(values, dtype=np.float64)
+            n, c = values.shape
+            ptr = _ptr(values)
+            if maximise.shape != (c,):
+                raise ValueError("lexicase_par: maximise must have one entry "
+                                 "per case (%d)" % c)
+        out = np.zeros(max(int(k), 1), dtype=np.int32)
+        failed = ctypes.c_int64(-1)
+        self._check(self.lib.gpe_lexicase_par(
+            self.h, ptr, n, c, _ptr(maximise), int(mode), float(epsilon),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(k), _ptr(out),
+            ctypes.byref(failed)), "gpe_lexicase_par")
+        return out[:int(k)], failed.value
+
+    def lexicase_bits_par(self, planes, n, n_cases, k, seed):
+        """gpe_lexicase_bits_par: :meth:`lexicase_par`'s rule on 0/1 hits,
+        every case maximised.  *planes* as :meth:`lexicase_bits` takes them
+        (None: the last run_hit_planes' matrix on the device)."""
+        if planes is None:
+            n, n_cases, ptr = 0, 0, None
+        else:
+            units = (int(n_cases) + 31) // 32
+            planes = np.ascontiguousarray(planes, dtype=np.uint32)
+            if planes.shape != (int(n), units):
+                raise ValueError("lexicase_bits_par: planes must be uint32 "
+                                 "[%d, %d]" % (n, units))
+            ptr = _ptr(planes)
+        out = np.zeros(max(int(k), 1), dtype=np.int32)
+        failed = ctypes.c_int64(-1)
+        self._check(self.lib.gpe_lexicase_bits_par(
+            self.h, ptr, int(n), int(n_cases),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(k), _ptr(out),
+            ctypes.byref(failed)), "gpe_lexicase_bits_par")
+        return out[:int(k)], failed.value
 
     def informed_cases(self, planes, n, n_cases, eps, seed, m):
         """gpe_informed_cases: the farthest-first subset of *m* cases

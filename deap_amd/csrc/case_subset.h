@@ -17,6 +17,8 @@
 //                  to the previous set;
 //   case_stale     set: d_case_out's rows have the previous set's stride, so
 //                  gpe_lexicase(NULL) refuses until a cases run writes it;
+//   case_t_valid   cleared: d_case_t is the case-major copy of that matrix
+//                  (gpe_lexicase_par(NULL) transposes again after the next run);
 //   hit_valid      cleared: d_hit's planes are the previous set's cases, so
 //                  gpe_lexicase_bits(NULL) refuses until a hit-planes run;
 //   ex_hcases      reset: the host exact pass copies the active cases back on
@@ -115,6 +117,7 @@ void subset_changed(gpe_ctx* ctx) {
   ctx->planned_mode = -1;
   ctx->last_mode = -1;
   ctx->case_stale = true;
+  ctx->case_t_valid = false;
   ctx->hit_valid = false;
   ctx->ex_hcases = false;
 }

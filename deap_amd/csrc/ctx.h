@@ -531,6 +531,39 @@ struct gpe_ctx {
   size_t inf_idx_cap = 0;
   int32_t* d_inf_dist = nullptr;
   size_t inf_dist_cap = 0;
+  // Parallel lexicase selection (gpe_lexicase_par / gpe_lexicase_bits_par,
+  // lexicase_par.h).  d_case_t: d_case_out case-major, double[case_t_cases]
+  // [case_t_n], transposed at the first gpe_lexicase_par(NULL) after a
+  // per-case run (case_t_valid; every per-case run and gpe_select_cases clear
+  // it); d_lexp_vt: a caller's host matrix transposed.  d_lexp_first /
+  // d_lexp_slot: per selection its opening case and the stats slot of that
+  // case; d_lexp_ucase / d_lexp_masks / d_lexp_counts: per distinct opening
+  // case its index, the survivors uint64[W] and their number; d_lexp_failed:
+  // the smallest failing selection (all ones: none); d_lexp_cand /
+  // d_lexp_vals: per-block slices for candidate words and compacted values
+  // that LDS does not hold.
+  double* d_case_t = nullptr;
+  size_t case_t_cap = 0;
+  bool case_t_valid = false;
+  int64_t case_t_n = 0, case_t_cases = 0;
+  double* d_lexp_vt = nullptr;
+  size_t lexp_vt_cap = 0;
+  int32_t* d_lexp_first = nullptr;
+  size_t lexp_first_cap = 0;
+  int32_t* d_lexp_slot = nullptr;
+  size_t lexp_slot_cap = 0;
+  int32_t* d_lexp_ucase = nullptr;
+  size_t lexp_ucase_cap = 0;
+  unsigned long long* d_lexp_masks = nullptr;
+  size_t lexp_masks_cap = 0;
+  int32_t* d_lexp_counts = nullptr;
+  size_t lexp_counts_cap = 0;
+  unsigned long long* d_lexp_failed = nullptr;
+  size_t lexp_failed_cap = 0;
+  unsigned long long* d_lexp_cand = nullptr;
+  size_t lexp_cand_cap = 0;
+  double* d_lexp_vals = nullptr;
+  size_t lexp_vals_cap = 0;
   char* h_pin_vals = nullptr;        // pinned staging of gpe_run_values' copy back
   size_t h_pin_vals_cap = 0;
   float ms[3] = {0, 0, 0};

@@ -1832,7 +1832,10 @@ void gpe_destroy(gpe_ctx* ctx) {
                   ctx->aasm_deep.d_part, ctx->d_jump_ac[0], ctx->d_jump_ac[1],
                   ctx->d_hit, ctx->d_hit_t, ctx->d_lexb_in, ctx->d_lexb_q,
                   ctx->d_lexb_scratch, ctx->d_inf_hit, ctx->d_inf_q, ctx->d_inf_mind,
-                  ctx->d_inf_part, ctx->d_inf_idx, ctx->d_inf_dist};
+                  ctx->d_inf_part, ctx->d_inf_idx, ctx->d_inf_dist, ctx->d_case_t,
+                  ctx->d_lexp_vt, ctx->d_lexp_first, ctx->d_lexp_slot, ctx->d_lexp_ucase,
+                  ctx->d_lexp_masks, ctx->d_lexp_counts, ctx->d_lexp_failed, ctx->d_lexp_cand,
+                  ctx->d_lexp_vals};
   if (ctx->comm && rccl().ok) (void)rccl().comm_destroy(ctx->comm);
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -2556,6 +2559,7 @@ int run_numpy(gpe_ctx* ctx, int mode, double* hi, double* lo,
   const size_t n = (size_t)ctx->n_prog * (size_t)ctx->n_cases;
   if (ensure(ctx, &ctx->d_case_out, &ctx->case_cap, n)) return GPE_E_HIP;
   ctx->case_stale = false;     // (written below, for the active case set)
+  ctx->case_t_valid = false;   // ... and its case-major copy is the old matrix's
   ctx->case_n = ctx->n_prog;   // ... by the loaded programs (gpe_informed_cases checks)
   if (mode == GPE_MODE_SSE_SEQ) {
     ctx->case_on = 1;
@@ -2709,6 +2713,7 @@ int gpe_run_cases(gpe_ctx* ctx, int mode, double* out_cases, double* out_hi,
   const size_t n = (size_t)ctx->n_prog * (size_t)ctx->n_cases;
   if (ensure(ctx, &ctx->d_case_out, &ctx->case_cap, n)) return GPE_E_HIP;
   ctx->case_stale = false;     // (written below, for the active case set)
+  ctx->case_t_valid = false;   // ... and its case-major copy is the old matrix's
   ctx->case_n = ctx->n_prog;   // ... by the loaded programs (gpe_informed_cases checks)
   ctx->case_on = 1;
   int rc = run_common(ctx, mode, ctx->d_hi, ctx->d_lo, ctx->d_err, ctx->d_flags);
@@ -2819,6 +2824,7 @@ int gpe_run_values_bits(gpe_ctx* ctx, uint32_t* out_planes) {
 
 #include "case_bits.h"
 #include "case_informed.h"
+#include "lexicase_par.h"
 
 namespace {
 int moments_check(gpe_ctx* ctx) {
@@ -3052,6 +3058,7 @@ int gpe_run_abserr_cases(gpe_ctx* ctx, double hit_eps, double* out_cases, double
   const size_t n = (size_t)ctx->n_prog * (size_t)ctx->n_cases;
   if (ensure(ctx, &ctx->d_case_out, &ctx->case_cap, n)) return GPE_E_HIP;
   ctx->case_stale = false;     // (written below, for the active case set)
+  ctx->case_t_valid = false;   // ... and its case-major copy is the old matrix's
   ctx->case_n = ctx->n_prog;   // ... by the loaded programs (gpe_informed_cases checks)
   // whatever way the run is left, the next abs-error run is a plain one
   struct Request {

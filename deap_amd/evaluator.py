@@ -771,6 +771,8 @@ class GPUEvaluator(object):
         # stay theirs) and results of the last evaluation that left a
         # per-case matrix on the GPU
         self._lex_batch = None
+        # select_lexicase(parallel=True): the seed its last call drew
+        self.last_lexicase_seed = None
         # informed_subsample: each pick's distance to the nearest earlier one
         self.last_informed_distances = np.zeros(0, dtype=np.int32)
 
@@ -1222,7 +1224,8 @@ class GPUEvaluator(object):
 
     LEXICASE_MODES = {"plain": 0, "epsilon": 1, "automatic": 2}
 
-    def select_lexicase(self, individuals, k, mode="automatic", epsilon=0.0):
+    def select_lexicase(self, individuals, k, mode="automatic", epsilon=0.0,
+                        parallel=False):
         """Lexicase selection of *k* individuals straight from the per-case
         matrix the last :meth:`evaluate` / :meth:`map` left on the GPU
         (:class:`SymbRegCaseAbsErrors` in either *cases* mode,
@@ -1251,7 +1254,19 @@ class GPUEvaluator(object):
         (``gpe_lexicase_bits``), which has neither of the limits above.
         ``epsilon >= 1`` raises ``ValueError``: past 1 every candidate
         survives every case and the selection is ``random.choice``; a
-        negative epsilon raises too."""
+        negative epsilon raises too.
+
+        *parallel* True selects with ``gpe_lexicase_par`` /
+        ``gpe_lexicase_bits_par``: the *k* selections run side by side, one
+        workgroup each, with neither of the limits above.  Each is still the
+        reference's loop body (a uniformly shuffled case order, the
+        reference's survivors, a uniform final pick), but the shuffles and
+        picks are SplitMix64 keys of one ``seed = random.getrandbits(64)``,
+        the only draw from ``random`` (kept in ``last_lexicase_seed``; the
+        rule is in include/gpeval.h, ``_lib.host_lexicase_par`` is its host
+        twin).  A seeded run is reproducible; its picks are not DEAP's for
+        the same ``random.seed``.  The checks above are made first, in the
+        same order, and ``k == 0`` returns ``[]`` before any draw."""
         if mode not in self.LEXICASE_MODES:
             raise ValueError("mode must be 'plain', 'epsilon' or 'automatic' "
                              "(got %r)" % (mode,))
@@ -1293,7 +1308,17 @@ class GPUEvaluator(object):
             return []
         if not individuals:               # individuals[0] in the reference
             raise IndexError("list index out of range")
-        if bits:
+        if parallel:
+            # the only draw: case orders and choices are keys of this seed
+            seed = random.getrandbits(64)
+            self.last_lexicase_seed = seed
+            if bits:
+                idx, failed = self.ctx.lexicase_bits_par(None, 0, 0, k, seed)
+            else:
+                idx, failed = self.ctx.lexicase_par(
+                    None, np.zeros(self.spec.n_cases, dtype=np.uint8), k,
+                    seed, self.LEXICASE_MODES[mode], epsilon)
+        elif bits:
             idx, failed = self.ctx.lexicase_bits(None, 0, 0, k, random._inst)
         else:
             idx, failed = self.ctx.lexicase(

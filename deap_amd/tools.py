@@ -126,11 +126,17 @@ def selAutomaticEpsilonLexicase(individuals, k):
 _LEX_CTX = {}
 
 
-def _lexicase_gpu(individuals, k, mode, epsilon=0.0, device=None):
+def _lexicase_gpu(individuals, k, mode, epsilon=0.0, device=None,
+                  parallel=False):
     """gpe_lexicase: the reference's selection loop on the GPU, drawing from
     the module ``random`` stream exactly as the reference does (its MT19937
     state goes to the device and comes back advanced), so a seeded run
-    selects the same individuals and continues with the same stream."""
+    selects the same individuals and continues with the same stream.
+
+    *parallel*: gpe_lexicase_par instead — the k selections side by side,
+    their case orders and picks keyed by one ``random.getrandbits(64)`` (the
+    only draw; the rule is in include/gpeval.h).  Reproducible from the seed,
+    but not the reference's picks."""
     import numpy as np
     from . import _lib
     from .evaluator import _default_device
@@ -144,34 +150,47 @@ def _lexicase_gpu(individuals, k, mode, epsilon=0.0, device=None):
     values = np.asarray([ind.fitness.values for ind in individuals],
                         dtype=np.float64)
     maximise = np.asarray(individuals[0].fitness.weights) > 0
-    idx, failed = _LEX_CTX[dev].lexicase(values, maximise, k, random._inst,
-                                         mode, epsilon)
+    if parallel:
+        idx, failed = _LEX_CTX[dev].lexicase_par(
+            values, maximise, k, random.getrandbits(64), mode, epsilon)
+    else:
+        idx, failed = _LEX_CTX[dev].lexicase(values, maximise, k,
+                                             random._inst, mode, epsilon)
     if failed >= 0:                       # random.choice([]) in the reference
         raise IndexError("Cannot choose from an empty sequence")
     return [individuals[i] for i in idx.tolist()]
 
 
-def selLexicaseGPU(individuals, k, device=None):
+def selLexicaseGPU(individuals, k, device=None, parallel=False):
     """Drop-in for :func:`selLexicase` (reference selection.py:214-244) that
-    filters on the GPU; same selections, same ``random`` consumption."""
-    return _lexicase_gpu(individuals, k, 0, device=device)
+    filters on the GPU; same selections, same ``random`` consumption.
+    *parallel* True: the selections run side by side from one drawn seed
+    (:func:`_lexicase_gpu`); lexicase selections, but not the same picks."""
+    return _lexicase_gpu(individuals, k, 0, device=device, parallel=parallel)
 
 
-def selEpsilonLexicaseGPU(individuals, k, epsilon, device=None):
-    """Drop-in for :func:`selEpsilonLexicase` (selection.py:247-281)."""
-    return _lexicase_gpu(individuals, k, 1, epsilon, device=device)
+def selEpsilonLexicaseGPU(individuals, k, epsilon, device=None,
+                          parallel=False):
+    """Drop-in for :func:`selEpsilonLexicase` (selection.py:247-281);
+    *parallel* as :func:`selLexicaseGPU`."""
+    return _lexicase_gpu(individuals, k, 1, epsilon, device=device,
+                         parallel=parallel)
 
 
 # the device kernel keeps a case's values for the medians in LDS
 AUTO_EPSILON_DEVICE_MAX = 16384
 
 
-def selAutomaticEpsilonLexicaseGPU(individuals, k, device=None):
+def selAutomaticEpsilonLexicaseGPU(individuals, k, device=None,
+                                   parallel=False):
     """Drop-in for :func:`selAutomaticEpsilonLexicase`
     (selection.py:283-320).  Above AUTO_EPSILON_DEVICE_MAX individuals the
     selection runs as :func:`selAutomaticEpsilonLexicase` on the host (same
     selections, same ``random`` consumption; selection is not on the
-    evaluation path)."""
+    evaluation path).  *parallel* as :func:`selLexicaseGPU`; that route has
+    no such limit and never falls back to the host."""
+    if parallel:
+        return _lexicase_gpu(individuals, k, 2, device=device, parallel=True)
     if len(individuals) > AUTO_EPSILON_DEVICE_MAX:
         return selAutomaticEpsilonLexicase(individuals, k)
     return _lexicase_gpu(individuals, k, 2, device=device)

@@ -404,6 +404,87 @@ int gpe_host_informed_cases(const uint32_t* planes, int64_t n, int64_t n_cases,
 int gpe_host_hit_threshold(const double* cases, int64_t n, int64_t n_cases,
                            double eps, uint32_t* out_planes);
 
+/* Parallel lexicase selection: k selections that do not share a random
+ * stream, one workgroup each.  gpe_lexicase / gpe_lexicase_bits replay
+ * CPython's MT19937 stream, where selection s + 1 starts at a position that
+ * depends on randbelow(count_s), the filter's result, so their selections run
+ * one after another.  Here the caller makes one draw, a 64-bit seed, and every
+ * selection's case order and final choice follow from it by this rule (the
+ * picks are reproducible from the seed; they are not DEAP's picks for the
+ * same random.seed).
+ *
+ * Keys.  K(i) is the (i + 1)-th output of SplitMix64 seeded with `seed`:
+ *   z = seed + (i + 1) * 0x9E3779B97F4A7C15;
+ *   z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *   z = (z ^ z >> 27) * 0x94D049BB133111EB;   K = z ^ z >> 31   (mod 2^64)
+ * (gpe_informed_cases' key).  K(0) = 0xE220A8397B1DCDAF for seed = 0,
+ * K(1) = 0x6E789E6AA1B965F4.
+ *
+ * For selection s in [0, k) over n individuals and C cases, with
+ * i0 = s * (C + 1) as a uint64:
+ * 1. Case order.  The cases are sorted ascending by (K(i0 + c), c).  The keys
+ *    compare as unsigned integers.
+ * 2. Filter.  This is the reference's loop (deap/tools/selection.py:214-320),
+ *    with the arithmetic gpe_lexicase uses.  It starts with all n candidates.
+ *    It continues while cases remain and more than one candidate is left.  A
+ *    case's best value is Python's max / min over the candidates in index
+ *    order, so a leading nan stays.  Mode 0 ("plain") keeps v == best.  Mode 1
+ *    ("epsilon") keeps v <= best + eps (>= best - eps where the case is
+ *    maximised).  Mode 2 ("automatic") uses numpy.median twice.  The median is
+ *    nan if any value is nan.  For an even count it is (a + b) / 2 of the two
+ *    middle values.  The MAD is the median of |v - med|, and takes eps' place.
+ *    All of it is fp64.
+ * 3. Choice.  With `count` survivors in ascending index order,
+ *    r = (K(i0 + C) * count) >> 64.  This is the high half of the 64 x 64
+ *    product.  The pick is the r-th survivor.  If count == 0, which happens
+ *    when a nan is the best value, then out[s] = -1 and the selection fails.
+ *    *failed is the smallest failing s, or -1 if none fails.
+ *
+ * values is a HOST double[n][n_cases], or NULL for the per-case matrix of the
+ * last gpe_run_cases / gpe_run_abserr_cases (n, n_cases are then the
+ * context's; GPE_E_STATE as gpe_lexicase).  maximise[n_cases] and mode /
+ * epsilon are gpe_lexicase's.  out is int32[k], filled for every selection.
+ * There is no limit on n or n_cases beyond memory: the matrix is read
+ * case-major (a transposed copy double[n_cases][n], cached until the next
+ * per-case run or gpe_select_cases), the first case of every selection is
+ * filtered once per distinct opening case, medians are an exact radix select
+ * on the doubles' order-preserving 64-bit image, and candidate words and
+ * compacted values live in LDS while they fit (gpe_lexicase_par_lds_values
+ * values) and in per-block device scratch otherwise.  The grid is
+ * min(k, 8 x CUs) persistent blocks; blocks never wait for each other.
+ * n <= 0, n > INT32_MAX, n_cases outside 1 .. 2^31 - 1, k < 0 or a mode
+ * outside 0..2: GPE_E_INVALID with a message.  k == 0 does nothing.  The call
+ * disturbs nothing else: the resident fitness, the per-case matrix, the hit
+ * planes and the active case set stay as they were. */
+int gpe_lexicase_par(gpe_ctx* ctx, const double* values, int64_t n,
+                     int64_t n_cases, const uint8_t* maximise, int mode,
+                     double epsilon, uint64_t seed, int64_t k, int32_t* out,
+                     int64_t* failed);
+
+/* The same rule on 0/1 hits with every case maximised, where the three modes
+ * (epsilon in [0, 1)) keep the same survivors (see gpe_lexicase_bits), so
+ * there is no mode: a case keeps cand & plane[c] when that is not empty, else
+ * every candidate.  planes is gpe_lexicase_bits' HOST matrix
+ * uint32[n][ceil(n_cases / 32)], or NULL for the matrix of the last
+ * gpe_run_hit_planes (GPE_E_STATE as there).  seed, k, out, failed and the
+ * argument errors are gpe_lexicase_par's. */
+int gpe_lexicase_bits_par(gpe_ctx* ctx, const uint32_t* planes, int64_t n,
+                          int64_t n_cases, uint64_t seed, int64_t k,
+                          int32_t* out, int64_t* failed);
+
+/* Host twin of gpe_lexicase_par on a host matrix (no GPU): the rule in plain
+ * C++.  Hit planes are checked against it unpacked to 0/1 doubles with
+ * maximise = 1 and mode 0.  GPE_E_INVALID for the arguments gpe_lexicase_par
+ * refuses and for a NULL values or maximise. */
+int gpe_host_lexicase_par(const double* values, int64_t n, int64_t n_cases,
+                          const uint8_t* maximise, int mode, double epsilon,
+                          uint64_t seed, int64_t k, int32_t* out,
+                          int64_t* failed);
+
+/* The number of compacted candidate values (doubles) a gpe_lexicase_par block
+ * keeps in LDS; larger candidate sets go through device scratch. */
+int64_t gpe_lexicase_par_lds_values(void);
+
 /* Device tournament selection that replays the reference's random stream:
  * selTournament (deap/tools/selection.py:51-69, aspirants drawn by selRandom
  * :15-28, i.e. random.choice) — k tournaments of tournsize aspirants, the
