@@ -67,6 +67,8 @@ SIGNATURES = {
     "gpe_lexicase": (_I, [_P, _P, _I64, _I64, _P, _I, ctypes.c_double, _P,
                           _I64, _P, ctypes.POINTER(_I64)]),
     "gpe_run_hit_planes": (_I, [_P, _P, _P, _P, _P]),
+    "gpe_run_typed_hit_planes": (_I, [_P, _P, _P, _P, _P]),
+    "gpe_host_typed_hit_planes": (_I, [_P, _P, _I64, _I64, _P]),
     "gpe_read_hit_planes": (_I, [_P, _P]),
     "gpe_host_hit_planes": (_I, [_P, _P, _I64, _I64, _P]),
     "gpe_lexicase_bits": (_I, [_P, _P, _I64, _I64, _P, _I64, _P,
@@ -276,6 +278,23 @@ def host_hit_planes(result_planes, out_plane, n_cases):
                                     int(n_cases), _ptr(out))
     if rc != 0:
         raise GpeError("gpe_host_hit_planes failed (%d)" % rc)
+    return out
+
+
+def host_typed_hit_planes(values, labels):
+    """Host twin of a typed hit-planes run's word arithmetic (CPU, no GPU):
+    program outputs ``float64[n, n_cases]`` against *labels* → hit planes
+    ``uint32[n, ceil(n_cases / 32)]``, bit c set where ``bool(value)`` is
+    ``bool(label)`` (a nan output is true); pad bits 0."""
+    v = np.ascontiguousarray(np.atleast_2d(values), dtype=np.float64)
+    lab = np.ascontiguousarray(labels, dtype=np.float64)
+    if lab.ndim != 1 or len(lab) < 1 or v.shape[1] != len(lab):
+        raise ValueError("values are [n, n_cases] and labels [n_cases]")
+    out = np.zeros((v.shape[0], (len(lab) + 31) // 32), dtype=np.uint32)
+    rc = load().gpe_host_typed_hit_planes(_ptr(v), _ptr(lab), v.shape[0],
+                                          len(lab), _ptr(out))
+    if rc != 0:
+        raise GpeError("gpe_host_typed_hit_planes failed (%d)" % rc)
     return out
 
 
@@ -912,6 +931,26 @@ class Context(object):
             self.h, _ptr(planes) if want_planes and n else None,
             _ptr(hits) if n else None, None, None), "gpe_run_hit_planes")
         return planes, hits
+
+    def run_typed_hit_planes(self, want_planes=True, want_err=True):
+        """gpe_run_typed_hit_planes → (planes uint32 [n_prog,
+        ceil(n_cases / 32)] or None, hits float64 [n_prog], first_err uint64
+        [n_prog] or None): a HITS_BOOL run of the F machine that also leaves
+        every program's hit plane on the device.  *want_planes* /
+        *want_err* False: no host copy of the matrix / the error words is
+        made or allocated."""
+        n = self.n_prog
+        units = (self.n_cases + 31) // 32
+        planes = np.zeros((n, units), dtype=np.uint32) if want_planes \
+            else None
+        hits = np.zeros(n, dtype=np.float64)
+        err = np.zeros(n, dtype=np.uint64) if want_err else None
+        self._check(self.lib.gpe_run_typed_hit_planes(
+            self.h, _ptr(planes) if want_planes and n else None,
+            _ptr(hits) if n else None, _ptr(err) if want_err and n else None,
+            None),
+            "gpe_run_typed_hit_planes")
+        return planes, hits, err
 
     def hit_planes(self, n):
         """gpe_read_hit_planes → uint32 [n, ceil(n_cases / 32)]: the bit

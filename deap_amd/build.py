@@ -40,6 +40,12 @@ ASM_OUT = [os.path.join(HERE, "csrc", "gp_asm_core.inc"),
            os.path.join(HERE, "csrc", "gp_asm_layout_typed.h"),
            os.path.join(HERE, "csrc", "gp_asm_core_exact_deep.inc"),
            os.path.join(HERE, "csrc", "gp_asm_layout_exact_deep.h")]
+# the typed core's hit-planes variant (TypedCaseHits): the same layout, END
+# also keeps the match masks; a file and a kernel of its own, so that the
+# count-only core's text does not change
+ASM_TYPED_HITS = ("2", "5", "64", "_typed_hits")
+ASM_HITS_OUT = [os.path.join(HERE, "csrc", "gp_asm_core_typed_hits.inc"),
+                os.path.join(HERE, "csrc", "gp_asm_layout_typed_hits.h")]
 ASM32_OUT = [os.path.join(HERE, "csrc", "gp_asm_core32.inc"),
              os.path.join(HERE, "csrc", "gp_asm_core32_deep.inc")]
 
@@ -85,6 +91,9 @@ def generate():
                            stdout=subprocess.DEVNULL, env=_gen_env())
         with open(_stamp(), "w") as fh:
             fh.write(want)
+    if _stale(ASM_HITS_OUT, [GEN]):
+        subprocess.run([sys.executable, GEN] + list(ASM_TYPED_HITS), check=True,
+                       stdout=subprocess.DEVNULL, env=_gen_env())
     if _stale(ASM32_OUT, [GEN, GEN32]):
         for args in (list(ASM32_VARIANT), _deep(ASM32_VARIANT)):
             subprocess.run([sys.executable, GEN32] + args, check=True,
@@ -95,14 +104,15 @@ def generate():
 LIB_HEADERS = ("lower_core.h", "trig_ranges.h", "host_pool.h", "bigint_host.h", "trig_dev.h", "exact_int.h",
                "rccl_layer.h", "select_dev.h", "ctx.h", "fb_kernels.h", "asm_kernels.h",
                "f_eval_asm_body.h", "planner.h", "exact_run.h", "moments.h", "abserr.h",
-               "case_subset.h", "case_bits.h", "case_informed.h", "lexicase_par.h")
+               "case_subset.h", "case_bits.h", "case_informed.h", "lexicase_par.h",
+               "typed_hits.h")
 
 
 def needs_build():
     if not os.path.exists(OUT):
         return True
     deps = [SRC, os.path.join(REPO, "include", "gpeval.h"), __file__, GEN,
-            GEN32] + [os.path.join(HERE, "csrc", h) for h in LIB_HEADERS] + ASM_OUT + ASM32_OUT
+            GEN32] + [os.path.join(HERE, "csrc", h) for h in LIB_HEADERS] + ASM_OUT + ASM_HITS_OUT + ASM32_OUT
     return any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps)
 
 

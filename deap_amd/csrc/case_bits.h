@@ -1,7 +1,8 @@
 // Part of gpeval.hip's single translation unit (included there once, in
 // order, after the values runs): per-case hit planes of the B machine and
 // lexicase selection on them — gpe_run_hit_planes, gpe_lexicase_bits,
-// gpe_host_hit_planes.
+// gpe_host_hit_planes — and the F machine's run into the same matrix,
+// gpe_run_typed_hit_planes (typed classifiers; its pieces are in typed_hits.h).
 //
 // A hit-planes run is a GPE_MODE_HITS_BITS run whose kernels (b_eval_hits,
 // b_eval_lanes_hits: fb_kernels.h) also store each program's hit plane
@@ -199,6 +200,58 @@ int gpe_run_hit_planes(gpe_ctx* ctx, uint32_t* out_planes, double* out_hi, uint6
   ctx->hit_valid = true;
   if (int rc_d = results_to_host(ctx, np, out_hi, nullptr, out_err, out_flags)) return rc_d;
   if (out_planes) return values_to_host(ctx, out_planes, ctx->d_hit, words * sizeof(uint32_t));
+  return 0;
+}
+
+// The F machine's twin (typed_hits.h): a GPE_MODE_HITS_BOOL run of the typed
+// classifiers whose routes also store the matches they count.
+int gpe_run_typed_hit_planes(gpe_ctx* ctx, uint32_t* out_planes, double* out_hi,
+                             uint64_t* out_err, uint32_t* out_flags) {
+  if (!ctx) return GPE_E_INVALID;
+  if (ctx->machine != GPE_MACHINE_F)
+    return fail(ctx, GPE_E_ARG,
+                "gpe_run_typed_hit_planes needs the F machine (typed classifiers, "
+                "GPE_MODE_HITS_BOOL); the B machine's hit planes are gpe_run_hit_planes");
+  if (ctx->prec != GPE_PREC_F64)
+    return fail(ctx, GPE_E_ARG, "gpe_run_typed_hit_planes needs fp64 (GPE_PREC_F64): the "
+                                "hit planes are the fp64 machine's");
+  if (ctx->nt != 1)
+    return fail(ctx, GPE_E_ARG, "gpe_run_typed_hit_planes needs exactly one target column "
+                                "(the labels)");
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->hit_valid = ctx->hit_t_valid = false;
+  if (ctx->n_prog <= 0) return 0;            // (as gpe_run: nothing to do)
+  const size_t np = (size_t)ctx->n_prog;
+  const int64_t units = (ctx->n_cases + 31) / 32;
+  const size_t words = np * (size_t)units;
+  if (ensure(ctx, &ctx->d_hit, &ctx->hit_cap, words)) return GPE_E_HIP;
+  // (every loaded program is in exactly one launch list, and each list's
+  // kernel writes all words of its programs' rows: no clear)
+  ctx->hits_on = 1;
+  const int rc = run_mode(ctx, GPE_MODE_HITS_BOOL, ctx->d_hi, ctx->d_lo, ctx->d_err, ctx->d_flags);
+  ctx->hits_on = 0;
+  if (rc) return rc;
+  keep_resident(ctx, GPE_MODE_HITS_BOOL, false);
+  ctx->hit_n = ctx->n_prog;
+  ctx->hit_cases = ctx->n_cases;
+  ctx->hit_units = units;
+  ctx->hit_valid = true;
+  if (int rc_d = results_to_host(ctx, np, out_hi, nullptr, out_err, out_flags)) return rc_d;
+  if (out_planes) return values_to_host(ctx, out_planes, ctx->d_hit, words * sizeof(uint32_t));
+  return 0;
+}
+
+int gpe_host_typed_hit_planes(const double* values, const double* labels, int64_t n,
+                              int64_t n_cases, uint32_t* out) {
+  if (n < 0 || n_cases <= 0 || !labels || (n > 0 && (!values || !out))) return GPE_E_INVALID;
+  const int64_t units = (n_cases + 31) / 32;
+  for (int64_t i = 0; i < n; ++i) {
+    uint32_t* row = out + i * units;
+    for (int64_t w = 0; w < units; ++w) row[w] = 0u;
+    for (int64_t c = 0; c < n_cases; ++c)       // (nan != 0: bool(nan) is True)
+      if ((values[i * n_cases + c] != 0.0) == (labels[c] != 0.0))
+        row[c >> 5] |= 1u << (c & 31);
+  }
   return 0;
 }
 

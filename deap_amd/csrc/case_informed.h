@@ -307,7 +307,9 @@ int gpe_informed_cases(gpe_ctx* ctx, const uint32_t* planes, int64_t n, int64_t 
                        int32_t* out_dist) {
   if (!ctx || !out_idx || !out_dist) return GPE_E_INVALID;
   HIPCHK(hipSetDevice(ctx->device));
-  const bool f_route = !planes && ctx->machine == GPE_MACHINE_F;
+  // (the F machine after a typed hit-planes run: its planes, as on the B
+  // machine; a later per-case run clears hit_valid and decides again)
+  const bool f_route = !planes && ctx->machine == GPE_MACHINE_F && !ctx->hit_valid;
   if (!planes) {
     if (f_route) {                 // the matrix of the last per-case run, thresholded
       if (!ctx->d_case_out || ctx->n_prog <= 0 || ctx->case_stale)

@@ -275,6 +275,12 @@ struct gpe_ctx {
   // program whether it runs there; its threaded code (translated on the
   // first HITS_BOOL run after a load)
   std::vector<uint32_t> asm_typed_table, jump_asm_typed;
+  // ... and of the hit-planes variant (f_eval_asm_typed_hits, typed_hits.h).
+  // typed_code_hits: d_acode_t holds that kernel's handler addresses (the
+  // first run of either kind after the other translates again)
+  std::vector<uint32_t> asm_typed_hits_table, jump_asm_typed_hits;
+  uint32_t* d_jump_asm_typed_hits = nullptr;
+  bool typed_code_hits = false;
   std::vector<uint32_t> asm_exact_deep_table, jump_asm_exact_deep;
   uint32_t* d_jump_asm_exact_deep = nullptr;
   // the values kernels' (f_eval_asm_values) jump words, by kJv* (each kernel
@@ -499,7 +505,14 @@ struct gpe_ctx {
   // first gpe_lexicase_bits(NULL) after the run (hit_t_valid).  d_lexb_in /
   // d_lexb_q: a caller's host matrix and its transpose; d_lexb_scratch: the
   // candidate words and the permutation where they do not fit LDS.
+  // On the F machine the matrix is a typed hit-planes run's
+  // (gpe_run_typed_hit_planes, typed_hits.h): hits_on then makes the
+  // HITS_BOOL routes store the matches they count; a per-case run
+  // (gpe_run_cases, gpe_run_abserr_cases) and a precision change clear
+  // hit_valid too.  d_lab_planes: the label plane and its complement.
   int hits_on = 0;
+  uint32_t* d_lab_planes = nullptr;
+  size_t lab_planes_cap = 0;
   uint32_t* d_hit = nullptr;
   size_t hit_cap = 0;
   int64_t hit_n = 0, hit_cases = 0, hit_units = 0;

@@ -370,6 +370,8 @@ int run_exact_host(gpe_ctx* ctx, int mode, const std::vector<int64_t>& ents, dou
     if (ctx->case_on)
       HIPCHK(hipMemcpy(case_dst(ctx) + (size_t)prog * nc, term.data(), nc * sizeof(double),
                        hipMemcpyHostToDevice));
+    if (ctx->hits_on && mode == GPE_MODE_HITS_BOOL)      // a typed hit-planes run
+      if (int rc_h = host_row_hit_plane(ctx, prog, term.data())) return rc_h;
   }
   if (ensure(ctx, &ctx->d_exh_rec, &ctx->exh_rec_cap, rec.size())) return GPE_E_HIP;
   uint64_t* d_rec = ctx->d_exh_rec;
@@ -445,6 +447,8 @@ int run_exact(gpe_ctx* ctx, int mode, double* hi, double* lo,
                        (const double*)ctx->d_ex_rows, nc, (const int32_t*)ctx->d_ex_progs,
                        i0, hi, lo);
     HIPCHK(hipGetLastError());
+    if (ctx->hits_on && mode == GPE_MODE_HITS_BOOL)      // a typed hit-planes run
+      if (int rc_h = launch_rows_hit_planes(ctx, i0, m)) return rc_h;
   }
   HIPCHK(hipEventRecord(ctx->ev_redo[1], ctx->stream));
   HIPCHK(hipEventSynchronize(ctx->ev_redo[1]));

@@ -240,8 +240,14 @@ __device__ __forceinline__ void f_stage(const Task& a, R* xs,
 // where the case raises ValueError); no term column is read (the task's nt
 // is 0), nothing is squared or summed, no flags and no partials are written;
 // the first ValueError still feeds first_err.
-template <int K, int D, int MODE, typename R, bool EXACT = false, bool VALUES = false>
+// HPLANES (a typed hit-planes run, typed_hits.h; HITS_BOOL only): case_out is
+// the hit-plane matrix uint32[n_prog][ceil(n_cases / 32)] — the ballot each
+// chain's count is taken from is also stored, as words 2 (t K + k) + {0, 1} of
+// the program's row (lanes 0 and 1, one word each; pad bits 0).
+template <int K, int D, int MODE, typename R, bool EXACT = false, bool VALUES = false,
+          bool HPLANES = false>
 __global__ __launch_bounds__(kFMaxBlock) void f_eval(Task a) {
+  static_assert(!HPLANES || (MODE == GPE_MODE_HITS_BOOL && !VALUES), "hit planes: HITS_BOOL");
   extern __shared__ double lds_d[];
   R* lds = (R*)lds_d;
   const int lane = threadIdx.x & 63;
@@ -342,7 +348,7 @@ __global__ __launch_bounds__(kFMaxBlock) void f_eval(Task a) {
             hi = s;
             lo = lo + e;
             if (a.case_out) a.case_out[(size_t)prog * a.n_cases + c] = sq;
-          } else if (a.case_out) {
+          } else if (!HPLANES && a.case_out) {
             const bool pred = T[k] != R(0);
             const bool lab = ts[k * 64 + lane] != R(0);
             a.case_out[(size_t)prog * a.n_cases + c] = (pred == lab) ? 1.0 : 0.0;
@@ -351,7 +357,15 @@ __global__ __launch_bounds__(kFMaxBlock) void f_eval(Task a) {
         if (MODE != GPE_MODE_MSE) {       // count matches with one ballot
           const bool match = c < a.n_cases &&
                              ((T[k] != R(0)) == (ts[k * 64 + lane] != R(0)));
-          hits += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(match));
+          const unsigned long long mm = __builtin_amdgcn_ballot_w64(match);
+          hits += (uint32_t)__popcll(mm);
+          if constexpr (HPLANES) {
+            const int64_t units = (a.n_cases + 31) / 32;
+            const int64_t w = 2 * (t * K + k) + lane;
+            if (lane < 2 && w < units)
+              ((uint32_t*)a.case_out)[(size_t)prog * (size_t)units + w] =
+                  (uint32_t)(mm >> (32 * lane));
+          }
         }
       }
       if (MODE == GPE_MODE_MSE) {

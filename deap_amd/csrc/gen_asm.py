@@ -156,7 +156,7 @@ if GLIBC4:
 
 class Gen(object):
     def __init__(self, K, D, NV, TB0=32, SB=None, exact=False, trig_group=0,
-                 loop=False, typed=False, tile_loop=False):
+                 loop=False, typed=False, tile_loop=False, hit_planes=False):
         if SB is None:                      # the exact core: 16 more SGPRs
             SB = 40 if exact else 56
         self.K, self.D, self.NV = K, D, NV
@@ -179,6 +179,12 @@ class Gen(object):
         # NOT and if_then_else; the loop's END counts hits (bool(T) is
         # bool(label)) instead of summing squared errors
         self.typed = typed
+        # hit_planes (the typed loop core's second variant, suffix
+        # "_typed_hits"): END also keeps the match masks it counts — chain
+        # k's 64-bit mask goes, as two words, into lane j of the in/out VGPR
+        # operands %[hp<k>lo], %[hp<k>hi] (program j's hit bits of this tile)
+        assert not hit_planes or (typed and loop)
+        self.hit_planes = hit_planes
         self.fams = FAMS_TYPED if typed else FAMS
         self.trig_group = trig_group or int(os.environ.get("GEN_ASM_TRIG_GROUP", "0"))
         # exact core: a wave whose arguments are all below 2.426265 skips
@@ -2662,6 +2668,11 @@ class Gen(object):
             self.e("s_cbranch_scc0 .Lnopf_%=")
             self.load_first_window(self.SPF)
             self.label(".Lnopf_")
+        if self.hit_planes:
+            # the lane select of every v_writelane below: M0 = j, set once
+            # (an SALU write of M0 needs one wait state before a VALU lane
+            # select reads it: the compares below are well past that)
+            self.e("s_mov_b32 m0, s%d" % self.SJ)
         for k in range(self.K):
             self.e("v_cmp_neq_f64_e64 %s, 0, %s" % (CA, self.p(self.T(k))))
             self.e("s_xnor_b64 %s, %s, %%[lab%d]" % (CA, CA, k))
@@ -2669,12 +2680,19 @@ class Gen(object):
             self.e("s_bcnt1_i32_b64 s%d, %s" % (B + min(k, 1), CA))
             if k:
                 self.e("s_add_u32 s%d, s%d, s%d" % (B, B, B + 1))
+            if self.hit_planes:
+                # the mask just counted: its halves into lane j (SALU wrote
+                # the pair: as the count's v_writelane, one s_nop first)
+                self.e("s_nop 0")
+                self.e("v_writelane_b32 %%[hp%dlo], s%d, m0" % (k, self.CA))
+                self.e("v_writelane_b32 %%[hp%dhi], s%d, m0" % (k, self.CA + 1))
         self.e("v_readlane_b32 s%d, %%[hacc], s%d" % (self.NXT, self.SJ))
         self.e("s_nop 1")
         self.e("s_add_u32 s%d, s%d, s%d" % (self.NXT, self.NXT, B))
         # (one SGPR operand per VALU instruction: the lane select in M0,
         # free at END; .Lnext resets it)
-        self.e("s_mov_b32 m0, s%d" % self.SJ)
+        if not self.hit_planes:
+            self.e("s_mov_b32 m0, s%d" % self.SJ)
         self.e("s_nop 0")
         self.e("v_writelane_b32 %%[hacc], s%d, m0" % self.NXT)
         self.e("s_add_u32 s%d, s%d, 1" % (self.SJ, self.SJ))
@@ -3149,7 +3167,8 @@ def emit(K, D, NV, suffix="", out_dir=HERE, trig_group=0):
     The library carries two fp64 cores: D = 5 (the fast one) and a deep one
     for programs that need more operand-stack slots."""
     exact = suffix in ("_exact", "_exact_deep")    # glibc sin/cos (redo pass)
-    typed = suffix == "_typed"
+    hit_planes = suffix == "_typed_hits"     # (the typed core, masks kept)
+    typed = suffix == "_typed" or hit_planes
     # the D = 5 core runs the wave's program loop itself (Gen.loop); its
     # registers start at GEN_ASM_TB0 (the caller keeps fewer registers live
     # across a looping core).  The typed core always loops.
@@ -3163,7 +3182,8 @@ def emit(K, D, NV, suffix="", out_dir=HERE, trig_group=0):
     tile_loop = suffix == "_exact" and loop and \
         os.environ.get("GEN_ASM_TILE_LOOP", "1") == "1"
     g = Gen(K, D, NV, TB0=tb0, exact=exact, loop=loop, typed=typed,
-            trig_group=trig_group, tile_loop=tile_loop).build()
+            trig_group=trig_group, tile_loop=tile_loop,
+            hit_planes=hit_planes).build()
     # experiment knob: reserve more VGPRs (clobbered, unused) to price the
     # occupancy a register-hungrier core would have
     g.vmax += int(os.environ.get("GEN_ASM_PAD_VGPRS", "0")) if not suffix else 0

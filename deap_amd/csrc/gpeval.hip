@@ -71,6 +71,8 @@
 #include "gp_asm_layout_exact.h"
 #include "gp_asm_core_typed.inc"
 #include "gp_asm_layout_typed.h"
+#include "gp_asm_core_typed_hits.inc"
+#include "gp_asm_layout_typed_hits.h"
 #include "gp_asm_core_exact_deep.inc"
 #include "gp_asm_layout_exact_deep.h"
 
@@ -591,6 +593,16 @@ constexpr CoreIds kIdsTyped = [] {
   return c;                              // (no sin/cos: H_TRIG stays -1)
 }();
 static_assert(asmcore_typed::WINDOW == asmcore::WINDOW, "one window size");
+// the hit-planes variant keeps the typed core's handler ids and registers
+// (its END is longer: handler offsets of its own)
+static_assert(asmcore_typed_hits::H_COUNT == asmcore_typed::H_COUNT &&
+                  asmcore_typed_hits::H_NOT == asmcore_typed::H_NOT &&
+                  asmcore_typed_hits::H_ITE0 == asmcore_typed::H_ITE0 &&
+                  asmcore_typed_hits::H_BIN0 == asmcore_typed::H_BIN0 &&
+                  asmcore_typed_hits::K == asmcore_typed::K &&
+                  asmcore_typed_hits::D == asmcore_typed::D &&
+                  asmcore_typed_hits::NV == asmcore_typed::NV,
+              "the hit-planes core keeps the typed core's layout");
 static_assert(32 + (3 + trig_ranges::kClasses) * 8 <= 128,
               "translate_device's pinned header holds the class counts");
 static_assert(asmcore32::H_COUNT == asmcore::H_COUNT &&
@@ -972,14 +984,18 @@ int translate_all(gpe_ctx* ctx) {
 // ctx->typed_ok).
 int translate_typed(gpe_ctx* ctx) {
   XlateTabs T{};
+  // (a hit-planes run: the words are handler addresses of that kernel's own
+  // copy of the variant core; the same buffers, typed_code_hits says whose)
+  const bool hits = ctx->hits_on != 0;
   for (int t = 0; t < 3; ++t) {
-    T.tab[t] = ctx->d_jump_asm_typed;
+    T.tab[t] = hits ? ctx->d_jump_asm_typed_hits : ctx->d_jump_asm_typed;
     T.ids[t] = kIdsTyped;
   }
   int rc = translate_device(ctx, nullptr, T, false, true, &ctx->d_acode_t, &ctx->acode_t_cap,
                             &ctx->d_astart_t, &ctx->astart_t_cap);
   if (rc) return rc;
   ctx->typed_valid = true;
+  ctx->typed_code_hits = hits;
   return 0;
 }
 
@@ -1121,6 +1137,9 @@ int init_asm(gpe_ctx* ctx) {
     return rc;
   if ((rc = probe(f_probe_asm_typed, ctx->d_cst, asmcore_typed::H_COUNT,
                   ctx->asm_typed_table, "typed asm")))
+    return rc;
+  if ((rc = probe(f_probe_asm_typed_hits, ctx->d_cst, asmcore_typed_hits::H_COUNT,
+                  ctx->asm_typed_hits_table, "typed hit-planes asm")))
     return rc;
   static_assert(asmcore_exact_deep::H_COUNT == asmcore_deep::H_COUNT &&
                     asmcore_exact_deep::H_SIN == asmcore_deep::H_SIN &&
@@ -1269,6 +1288,29 @@ int init_asm(gpe_ctx* ctx) {
                                        2 * K * 64 * sizeof(double), ctx->stream, t);
                   }, ctx->asm_typed_table, ctx->jump_asm_typed, "typed asm")) ||
       (rc = jumps([&](uint32_t* d) {
+                    constexpr int K = asmcore_typed_hits::K;
+                    AsmTask t{};
+                    t.code = (const uint32_t*)scratch_buf(64 * sizeof(uint32_t));
+                    t.start = (const uint32_t*)scratch_buf(sizeof(uint32_t));
+                    t.slot_prog = (const int32_t*)scratch_buf(sizeof(int32_t));
+                    t.n_slots = 1;
+                    t.P = 1;
+                    t.X = (const double*)scratch_buf(K * 64 * sizeof(double));
+                    t.nv = 1;
+                    t.terms = (const double*)scratch_buf(K * 64 * sizeof(double));
+                    t.nt = 1;
+                    t.n_cases = K * 64;
+                    t.n_tiles = 1;
+                    t.tiles_per_group = 1;
+                    t.part = (double*)scratch_buf(2 * sizeof(double));
+                    // (the probe leaves the tile loop before the plane stores)
+                    t.case_out = (double*)scratch_buf(2 * K * sizeof(uint32_t));
+                    t.base_probe = d;
+                    hipLaunchKernelGGL(f_eval_asm_typed_hits, dim3(1, 1), dim3(64),
+                                       2 * K * 64 * sizeof(double), ctx->stream, t);
+                  }, ctx->asm_typed_hits_table, ctx->jump_asm_typed_hits,
+                  "typed hit-planes asm")) ||
+      (rc = jumps([&](uint32_t* d) {
                     hipLaunchKernelGGL(asm_values, dim3(1), dim3(64),
                                        kTrigLdsBytes + asmcore::K * 64 * sizeof(double),
                                        ctx->stream,
@@ -1309,6 +1351,7 @@ int init_asm(gpe_ctx* ctx) {
       upload(ctx->jump_asm32, &ctx->d_jump_asm32) ||
       upload(ctx->jump_asm32_deep, &ctx->d_jump_asm32_deep) ||
       upload(ctx->jump_asm_typed, &ctx->d_jump_asm_typed) ||
+      upload(ctx->jump_asm_typed_hits, &ctx->d_jump_asm_typed_hits) ||
       upload(ctx->jump_asm_exact_deep, &ctx->d_jump_asm_exact_deep))
     return GPE_E_HIP;
   for (int k = 0; k < kJvCount; ++k)
@@ -1331,7 +1374,12 @@ int plan_mode(gpe_ctx* ctx, int mode) {
   // kind after the other translates (and plans) again
   const bool xlate = asm_mode && (ctx->acode_prec != ctx->prec ||
                                   ctx->acode_values != ctx->values_on);
-  if (ctx->planned_mode == mode && !xlate) return 0;
+  // (likewise the typed core's code: a hit-planes run's kernel is not the
+  // count run's)
+  const bool txlate = ctx->machine == GPE_MACHINE_F && mode == GPE_MODE_HITS_BOOL &&
+                      ctx->typed_valid && ctx->typed_code_hits != (ctx->hits_on != 0);
+  if (txlate) ctx->typed_valid = false;
+  if (ctx->planned_mode == mode && !xlate && !txlate) return 0;
   if (xlate) {
     int rc0 = translate_all(ctx);
     if (rc0) return rc0;
@@ -1458,6 +1506,7 @@ int launch_cpp(gpe_ctx* ctx, int mode, Launch& fastL, Launch& deepL,
 }
 
 }  // namespace
+#include "typed_hits.h"
 #include "exact_run.h"
 #include "case_subset.h"
 namespace {
@@ -1536,6 +1585,7 @@ int run_common(gpe_ctx* ctx, int mode, double* hi, double* lo,
                        ctx->d_kc, nk, (double)ctx->label_true,
                        (double)(ctx->n_cases - ctx->label_true), hi, lo);
     HIPCHK(hipGetLastError());
+    if (ctx->hits_on && (rc = launch_const_hit_planes(ctx))) return rc;
   }
   if ((rc = launch_cpp(ctx, mode, ctx->fast, ctx->deep, err, flags))) return rc;
   HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
@@ -1835,7 +1885,7 @@ void gpe_destroy(gpe_ctx* ctx) {
                   ctx->d_inf_part, ctx->d_inf_idx, ctx->d_inf_dist, ctx->d_case_t,
                   ctx->d_lexp_vt, ctx->d_lexp_first, ctx->d_lexp_slot, ctx->d_lexp_ucase,
                   ctx->d_lexp_masks, ctx->d_lexp_counts, ctx->d_lexp_failed, ctx->d_lexp_cand,
-                  ctx->d_lexp_vals};
+                  ctx->d_lexp_vals, ctx->d_jump_asm_typed_hits, ctx->d_lab_planes};
   if (ctx->comm && rccl().ok) (void)rccl().comm_destroy(ctx->comm);
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -2559,6 +2609,9 @@ int run_numpy(gpe_ctx* ctx, int mode, double* hi, double* lo,
   const size_t n = (size_t)ctx->n_prog * (size_t)ctx->n_cases;
   if (ensure(ctx, &ctx->d_case_out, &ctx->case_cap, n)) return GPE_E_HIP;
   ctx->case_stale = false;     // (written below, for the active case set)
+  // (the F machine's hit planes, gpe_run_typed_hit_planes: the most recent
+  // per-case run decides what gpe_informed_cases(NULL) reads)
+  if (ctx->machine == GPE_MACHINE_F) ctx->hit_valid = false;
   ctx->case_t_valid = false;   // ... and its case-major copy is the old matrix's
   ctx->case_n = ctx->n_prog;   // ... by the loaded programs (gpe_informed_cases checks)
   if (mode == GPE_MODE_SSE_SEQ) {
@@ -2627,6 +2680,8 @@ int gpe_set_precision(gpe_ctx* ctx, int prec) {
   if (prec != GPE_PREC_F64 && prec != GPE_PREC_F32)
     return fail(ctx, GPE_E_INVALID, "precision must be GPE_PREC_F64 or GPE_PREC_F32");
   if (prec != ctx->prec) ctx->planned_mode = -1;
+  // (the F machine's hit planes are the fp64 machine's)
+  if (prec != ctx->prec && ctx->machine == GPE_MACHINE_F) ctx->hit_valid = false;
   ctx->prec = prec;
   return 0;
 }
@@ -2713,6 +2768,9 @@ int gpe_run_cases(gpe_ctx* ctx, int mode, double* out_cases, double* out_hi,
   const size_t n = (size_t)ctx->n_prog * (size_t)ctx->n_cases;
   if (ensure(ctx, &ctx->d_case_out, &ctx->case_cap, n)) return GPE_E_HIP;
   ctx->case_stale = false;     // (written below, for the active case set)
+  // (the F machine's hit planes, gpe_run_typed_hit_planes: the most recent
+  // per-case run decides what gpe_informed_cases(NULL) reads)
+  if (ctx->machine == GPE_MACHINE_F) ctx->hit_valid = false;
   ctx->case_t_valid = false;   // ... and its case-major copy is the old matrix's
   ctx->case_n = ctx->n_prog;   // ... by the loaded programs (gpe_informed_cases checks)
   ctx->case_on = 1;
@@ -3058,6 +3116,9 @@ int gpe_run_abserr_cases(gpe_ctx* ctx, double hit_eps, double* out_cases, double
   const size_t n = (size_t)ctx->n_prog * (size_t)ctx->n_cases;
   if (ensure(ctx, &ctx->d_case_out, &ctx->case_cap, n)) return GPE_E_HIP;
   ctx->case_stale = false;     // (written below, for the active case set)
+  // (the F machine's hit planes, gpe_run_typed_hit_planes: the most recent
+  // per-case run decides what gpe_informed_cases(NULL) reads)
+  if (ctx->machine == GPE_MACHINE_F) ctx->hit_valid = false;
   ctx->case_t_valid = false;   // ... and its case-major copy is the old matrix's
   ctx->case_n = ctx->n_prog;   // ... by the loaded programs (gpe_informed_cases checks)
   // whatever way the run is left, the next abs-error run is a plain one

@@ -344,6 +344,12 @@ int launch_f(gpe_ctx* ctx, Launch& L, bool deep, unsigned long long* err,
   if constexpr (MODE == GPE_MODE_MSE) {
     if (ctx->values_on) kern = f_eval<K, D, MODE, R, EXACT, true>;
   }
+  if constexpr (MODE == GPE_MODE_HITS_BOOL && std::is_same<R, double>::value && !EXACT) {
+    if (ctx->hits_on) {              // gpe_run_typed_hit_planes: the planes too
+      kern = f_eval<K, D, MODE, R, EXACT, false, true>;
+      a.case_out = (double*)ctx->d_hit;      // uint32[n_prog][n_units]
+    }
+  }
   HIPCHK(hipFuncSetAttribute((const void*)kern,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   dim3 grid((unsigned)L.groups, (unsigned)(L.waves / L.wpb));
@@ -458,9 +464,23 @@ int launch_asm_typed(gpe_ctx* ctx, Launch& L) {
   a.part = L.d_part;
   const size_t lds = lds_bytes_typed(ctx);
   L.lds = lds;
+  dim3 grid((unsigned)L.groups, (unsigned)(L.waves / L.wpb));
+  if (ctx->hits_on) {
+    // a hit-planes run (typed_hits.h): the variant kernel, whose own copy of
+    // the core the code was translated for (typed_code_hits)
+    if (!ctx->typed_code_hits || !ctx->d_hit)
+      return fail(ctx, GPE_E_STATE, "typed hit planes: code not translated for the kernel");
+    a.case_out = (double*)ctx->d_hit;        // uint32[n_prog][n_units]
+    HIPCHK(hipFuncSetAttribute((const void*)f_eval_asm_typed_hits,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(f_eval_asm_typed_hits, grid, dim3(64 * L.wpb), lds, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  if (ctx->typed_code_hits)
+    return fail(ctx, GPE_E_STATE, "typed core: code translated for the hit-planes kernel");
   HIPCHK(hipFuncSetAttribute((const void*)f_eval_asm_typed,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  dim3 grid((unsigned)L.groups, (unsigned)(L.waves / L.wpb));
   hipLaunchKernelGGL(f_eval_asm_typed, grid, dim3(64 * L.wpb), lds, ctx->stream, a);
   HIPCHK(hipGetLastError());
   return 0;

@@ -126,10 +126,10 @@ def _check_shardable(spec, case_sharded):
                                   "shards, but no sharded abs-error run is "
                                   "built" % type(spec).__name__)
     if getattr(spec, "hit_planes", False):
-        raise NotImplementedError("BooleanCaseHits runs on one GPU: the hit "
+        raise NotImplementedError("%s runs on one GPU: the hit "
                                   "planes stay in one context's memory for "
                                   "select_lexicase and are not gathered "
-                                  "across ranks")
+                                  "across ranks" % type(spec).__name__)
     if getattr(spec, "per_case", False):
         raise NotImplementedError("per-case outputs are not gathered across "
                                   "ranks; evaluate per-case specs on one GPU")

@@ -28,6 +28,7 @@ import copy
 import math
 import os
 import random
+import sys
 import time
 import warnings
 from functools import partial
@@ -52,8 +53,8 @@ __all__ = ["SymbRegMSE", "SymbRegNumpySSE", "SymbRegSumSSE",
            "SymbRegCaseAbsErrors",
            "BooleanHits", "BooleanCaseHits",
            "exact_dd_sums", "check_case_subset",
-           "TypedBoolHits", "GPUEvaluator", "gpu_map", "pack_bitplanes",
-           "unpack_bitplanes", "plan_predict_chunks", "first_error_cases",
+           "TypedBoolHits", "TypedCaseHits", "GPUEvaluator", "gpu_map",
+           "pack_bitplanes", "unpack_bitplanes", "plan_predict_chunks", "first_error_cases",
            "predict_error"]
 
 
@@ -453,6 +454,12 @@ def unpack_bitplanes(planes, n_cases):
     planes = np.ascontiguousarray(planes, dtype=np.uint32)
     if planes.ndim == 1:
         planes = planes[None, :]
+    if sys.byteorder == "little":
+        # a word's bytes in memory order are cases 0-7, 8-15, ...: one byte
+        # per case at once, with no uint32 per case in between (the host
+        # side of last_case_hits at 16,384 x 4,601 is this function)
+        bits = np.unpackbits(planes.view(np.uint8), axis=1, bitorder="little")
+        return bits[:, :n_cases].astype(bool)
     shifts = np.arange(32, dtype=np.uint32)
     bits = (planes[:, :, None] >> shifts) & np.uint32(1)
     return bits.reshape(planes.shape[0], -1)[:, :n_cases].astype(bool)
@@ -624,6 +631,58 @@ class TypedBoolHits(object):
         return out
 
 
+class TypedCaseHits(TypedBoolHits):
+    """Per-case hits ``bool(func(*row)) is bool(label)`` of a typed
+    classifier (spambase.py:70), for lexicase selection and informed
+    down-sampling, with :class:`TypedBoolHits`' count from the same GPU pass
+    (``gpe_run_typed_hit_planes``): one bit per individual and case, stored
+    by the typed core's hit-planes variant, by the C++ kernels (programs past
+    the core's five stack slots), by a fill (one-constant programs) and by the
+    exact-integer pass, each next to its count.
+
+    *cases* ``"host"`` (default): an individual's fitness is
+    ``tuple(int(bool(func(*row)) is bool(label)) for row, label in ...)``,
+    ``n_cases`` ints 0/1 (weights ``(1.0,) * n_cases``) for
+    ``tools.selLexicase*``.  ``"device"``: no ``n x n_cases`` matrix is
+    allocated or copied; the fitness is ``(hits,)`` as :class:`TypedBoolHits`
+    gives it and the bit matrix stays on the GPU.  Either way ``last_hits``
+    (int64) is filled and :meth:`GPUEvaluator.last_case_hits`,
+    :meth:`GPUEvaluator.select_lexicase` (every mode, *parallel* too),
+    :meth:`GPUEvaluator.informed_subsample` and
+    :meth:`GPUEvaluator.subsample` work as for :class:`BooleanCaseHits`.  An
+    individual that raises (the exact pass's ``OverflowError``, a tree taller
+    than the parser allows) is returned in its place.  fp64, one GPU."""
+    hit_planes = True
+    typed_planes = True
+
+    def __init__(self, X, labels, cases="host"):
+        TypedBoolHits.__init__(self, X, labels)
+        if cases not in ("host", "device"):
+            raise ValueError("cases must be 'host' or 'device' (got %r)"
+                             % (cases,))
+        self.cases = cases
+
+    def finish(self, i, hi, lo, err, flags, cases=None):
+        if err is not None and err != _lib.GPE_NO_ERROR:
+            return _case_error(err)
+        if self.cases == "device":
+            return (int(hi),)
+        return tuple(unpack_bitplanes(cases, self.n_cases)[0]
+                     .astype(np.int64).tolist())
+
+    def finish_all(self, hi, lo, err, flags, cases=None):
+        if self.cases == "device":
+            return TypedBoolHits.finish_all(self, hi, lo, err, flags)
+        if not len(hi):
+            return []
+        rows = unpack_bitplanes(cases, self.n_cases).astype(np.int64).tolist()
+        out = [tuple(row) for row in rows]
+        if err is not None:
+            for i in np.flatnonzero(err != np.uint64(_lib.GPE_NO_ERROR)).tolist():
+                out[i] = _case_error(err[i])
+        return out
+
+
 # ------------------------------------------------------------- evaluator --
 def trig_leaf_columns(pset_spec, spec, precision="fp64"):
     """Argument indices whose sin/cos leaves may be read from device columns:
@@ -693,7 +752,13 @@ class GPUEvaluator(object):
         for throughput, with the agreement DESIGN.md §4 states."""
         if precision not in ("fp64", "fp32"):
             raise ValueError("precision must be 'fp64' or 'fp32'")
-        if getattr(spec, "hit_planes", False):
+        if getattr(spec, "typed_planes", False) and precision != "fp64":
+            raise NotImplementedError(
+                "%s needs precision='fp64': the typed core's hit planes are "
+                "the fp64 machine's (gpe_run_typed_hit_planes)"
+                % type(spec).__name__)
+        if getattr(spec, "hit_planes", False) and \
+                not getattr(spec, "typed_planes", False):
             for p in (pset if isinstance(pset, (list, tuple)) else [pset]):
                 if getattr(p, "ret", object) is not object:
                     raise NotImplementedError(
@@ -835,9 +900,9 @@ class GPUEvaluator(object):
         order, no duplicates.
 
         Evaluate a sample of the parents on all cases first
-        (``subsample(None)``; :class:`BooleanCaseHits` or
-        :class:`SymbRegCaseAbsErrors`, either *cases* mode).  Two cases are as
-        far apart as the number of those individuals that pass one and fail
+        (``subsample(None)``; :class:`BooleanCaseHits`, :class:`TypedCaseHits`
+        or :class:`SymbRegCaseAbsErrors`, either *cases* mode).  Two cases are
+        as far apart as the number of those individuals that pass one and fail
         the other; for the regression spec a case is passed when its absolute
         error is finite and ``<= eps`` (default ``spec.hit_eps``; *eps* with
         :class:`BooleanCaseHits` is a ``ValueError``).  The first case is
@@ -1151,9 +1216,15 @@ class GPUEvaluator(object):
                 self.spec.figures(hi, err, flags)
         elif getattr(self.spec, "hit_planes", False):
             # (the hit planes in cases' place; the counts alone come back)
-            cases, hi = self.ctx.run_hit_planes(
-                want_planes=self.spec.cases == "host")
             lo = err = flags = None
+            if getattr(self.spec, "typed_planes", False):
+                # (the error words only where a program can raise: _want)
+                cases, hi, err = self.ctx.run_typed_hit_planes(
+                    want_planes=self.spec.cases == "host",
+                    want_err=want is None or "err" in want)
+            else:
+                cases, hi = self.ctx.run_hit_planes(
+                    want_planes=self.spec.cases == "host")
             self.last_hits = np.asarray(hi).astype(np.int64)
         elif getattr(self.spec, "per_case", False):
             cases, hi, lo, err, flags = self.ctx.run_cases(
@@ -1243,7 +1314,8 @@ class GPUEvaluator(object):
         for ``"automatic"``; ``n/32 + n_cases`` words within 48 KiB of LDS)
         are raised as the library words them.
 
-        After a :class:`BooleanCaseHits` evaluation the values are 0/1 hits
+        After a :class:`BooleanCaseHits` or :class:`TypedCaseHits` evaluation
+        the values are 0/1 hits
         and every case is maximised.  On such values ``selLexicase``,
         ``selEpsilonLexicase`` with ``0 <= epsilon < 1`` and
         ``selAutomaticEpsilonLexicase`` select the same individuals with the
@@ -1330,8 +1402,8 @@ class GPUEvaluator(object):
 
     def last_case_hits(self):
         """``bool[n, n_cases]``: the hit matrix of the last
-        :class:`BooleanCaseHits` evaluation, read back from the device's bit
-        matrix on request (either *cases* mode).  ``ValueError`` when the
+        :class:`BooleanCaseHits` / :class:`TypedCaseHits` evaluation, read
+        back from the device's bit matrix on request (either *cases* mode).  ``ValueError`` when the
         last evaluate / map left none (as :meth:`select_lexicase`)."""
         if not getattr(self.spec, "hit_planes", False) or \
                 self._lex_batch is None:

@@ -331,7 +331,43 @@ int gpe_lexicase(gpe_ctx* ctx, const double* values, int64_t n,
 int gpe_run_hit_planes(gpe_ctx* ctx, uint32_t* out_planes, double* out_hi,
                        uint64_t* out_err, uint32_t* out_flags);
 
-/* The resident bit matrix of the last gpe_run_hit_planes into the HOST array
+/* A typed hit-planes run (F machine, fp64, exactly one target column: the
+ * labels): gpe_run in GPE_MODE_HITS_BOOL in every respect — the same counts in
+ * out_hi, the same errors and flags, the same resident fitness for
+ * gpe_tournament(NULL) — whose routes, in the same pass, also store the matches
+ * they count into the context's hit-plane matrix
+ * uint32[n_prog][ceil(n_cases / 32)] (gpe_run_hit_planes' layout: bit c % 32
+ * of word c / 32 is 1 where bool(program(case c)) is bool(label c); bits past
+ * n_cases are 0; popcount(row) == out_hi).  The routes: the typed asm core's
+ * hit-planes variant (END's match masks, 128 cases a tile: lane l of chain k
+ * is case 128 t + 64 k + l, words 4 t + 2 k + {0, 1}), the C++ interpreter
+ * kernels for programs past the core's five stack slots (the count's
+ * ballots), a fill for one-constant programs (the label plane or its
+ * complement), and the exact-integer pass (its 0/1 terms).  out_planes: the
+ * HOST copy, or NULL to leave the matrix on the device, where
+ * gpe_lexicase_bits(NULL), gpe_lexicase_bits_par(NULL),
+ * gpe_informed_cases(NULL) and gpe_read_hit_planes take it.  GPE_E_ARG with a
+ * message on the B machine, in fp32, or with another number of target columns.
+ * Residency: gpe_select_cases, gpe_set_cases, a precision change and a
+ * per-case run (gpe_run_cases, gpe_run_abserr_cases) drop the planes; loading
+ * programs leaves them (the NULL routes refuse while the program count
+ * differs).  gpe_informed_cases(NULL) on the F machine reads whichever the
+ * most recent per-case run of the loaded programs left: these planes (eps is
+ * ignored, as on the B machine) or the double matrix (thresholded by eps).
+ * Replaces: bool(func(*row)) is bool(label) per row before the sum
+ * (spambase.py:70), the per-case fitness lexicase selection reads. */
+int gpe_run_typed_hit_planes(gpe_ctx* ctx, uint32_t* out_planes, double* out_hi,
+                             uint64_t* out_err, uint32_t* out_flags);
+
+/* Host twin of a typed hit-planes run's word arithmetic (no GPU): out[n]
+ * [ceil(n_cases / 32)] from program outputs values[n][n_cases] and
+ * labels[n_cases]: bit c is (values[i][c] != 0) == (labels[c] != 0) (a nan
+ * output is true, as bool(nan)); pad bits 0. */
+int gpe_host_typed_hit_planes(const double* values, const double* labels, int64_t n,
+                              int64_t n_cases, uint32_t* out);
+
+/* The resident bit matrix of the last gpe_run_hit_planes /
+ * gpe_run_typed_hit_planes into the HOST array
  * out_planes uint32[n_prog][n_units]; GPE_E_STATE when none is resident. */
 int gpe_read_hit_planes(gpe_ctx* ctx, uint32_t* out_planes);
 
