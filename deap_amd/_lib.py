@@ -85,6 +85,9 @@ SIGNATURES = {
     "gpe_host_lexicase_par": (_I, [_P, _I64, _I64, _P, _I, ctypes.c_double,
                                    ctypes.c_uint64, _I64, _P, _P]),
     "gpe_lexicase_par_lds_values": (_I64, []),
+    "gpe_hit_group_counts": (_I, [_P, _P, _I64, _I64, _P, _I, _P]),
+    "gpe_host_hit_group_counts": (_I, [_P, _I64, _I64, _P, _I, _P]),
+    "gpe_last_hit_group_ms": (_I, [_P, ctypes.POINTER(ctypes.c_float)]),
     "gpe_set_lowering": (_I, [_P, _I, _I, _P, _I, _P, _I]),
     "gpe_lower_programs": (_I, [_P, _P, _P, _I64, _P, _P, _P, _P, _P]),
     "gpe_lower_begin": (_I, [_P, _I64]),
@@ -334,6 +337,36 @@ def host_hit_threshold(cases, eps):
     if rc != 0:
         raise GpeError("gpe_host_hit_threshold failed (%d)" % rc)
     return out
+
+
+HIT_GROUPS_MAX = 8
+
+
+def _check_group_masks(what, masks, n_cases):
+    """The masks of a hit_group_counts call as uint32 ``[G, n_units]``."""
+    units = (int(n_cases) + 31) // 32
+    masks = np.ascontiguousarray(masks, dtype=np.uint32)
+    if masks.ndim != 2 or masks.shape[1] != units:
+        raise ValueError("%s: masks must be uint32 [G, %d] for %d cases"
+                         % (what, units, n_cases))
+    return masks
+
+
+def host_hit_group_counts(planes, n_cases, masks):
+    """Host twin of :meth:`Context.hit_group_counts` (CPU, no GPU): a
+    program-major hit matrix ``uint32[n, ceil(n_cases / 32)]`` and masks
+    ``uint32[G, ceil(n_cases / 32)]`` → ``int64[n, G]``,
+    ``popcount(row & mask)`` with the masks' pad bits cleared."""
+    planes = _check_planes("host_hit_group_counts", planes, n_cases)
+    masks = _check_group_masks("host_hit_group_counts", masks, n_cases)
+    n, G = planes.shape[0], masks.shape[0]
+    out = np.zeros((n, max(G, 1)), dtype=np.int32)
+    rc = load().gpe_host_hit_group_counts(
+        _ptr(planes) if n else None, n, int(n_cases), _ptr(masks), G,
+        _ptr(out) if n else None)
+    if rc != 0:
+        raise GpeError("gpe_host_hit_group_counts failed (%d)" % rc)
+    return out[:, :G].astype(np.int64)
 
 
 def lexicase_par_lds_values():
@@ -1034,6 +1067,40 @@ class Context(object):
             int(seed) & 0xFFFFFFFFFFFFFFFF, int(k), _ptr(out),
             ctypes.byref(failed)), "gpe_lexicase_bits_par")
         return out[:int(k)], failed.value
+
+    def hit_group_counts(self, planes, n, n_cases, masks):
+        """gpe_hit_group_counts → ``int64[n, G]``: ``popcount(row & mask)``
+        of every program's hit plane and each of the *G* (1 .. 8) *masks*
+        uint32 ``[G, ceil(n_cases / 32)]``.  *planes* as :meth:`lexicase_bits`
+        takes them, or None for the resident matrix of the loaded programs
+        (*n*, *n_cases* are then the context's).  The masks' pad bits are
+        cleared by the library; nothing resident is disturbed."""
+        if planes is None:
+            masks = _check_group_masks("hit_group_counts", masks, self.n_cases)
+            rows, n, n_cases, ptr = self.n_prog, 0, 0, None
+        else:
+            masks = _check_group_masks("hit_group_counts", masks, n_cases)
+            planes = np.ascontiguousarray(planes, dtype=np.uint32)
+            if planes.shape != (int(n), masks.shape[1]):
+                raise ValueError("hit_group_counts: planes must be uint32 "
+                                 "[%d, %d]" % (n, masks.shape[1]))
+            rows, ptr = int(n), planes
+        G = masks.shape[0]
+        out = np.zeros((max(rows, 1), max(G, 1)), dtype=np.int32)
+        if ptr is not None:
+            # (a matrix of no rows is still the caller's, not the resident one)
+            ptr = _ptr(planes if planes.size else out)
+        self._check(self.lib.gpe_hit_group_counts(
+            self.h, ptr, int(n), int(n_cases), _ptr(masks), G, _ptr(out)),
+            "gpe_hit_group_counts")
+        return out[:rows, :G].astype(np.int64)
+
+    def hit_group_ms(self):
+        """Device ms of the last :meth:`hit_group_counts`' kernel."""
+        ms = ctypes.c_float(0.0)
+        self._check(self.lib.gpe_last_hit_group_ms(self.h, ctypes.byref(ms)),
+                    "gpe_last_hit_group_ms")
+        return float(ms.value)
 
     def informed_cases(self, planes, n, n_cases, eps, seed, m):
         """gpe_informed_cases: the farthest-first subset of *m* cases

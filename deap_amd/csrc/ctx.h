@@ -577,6 +577,14 @@ struct gpe_ctx {
   size_t lexp_cand_cap = 0;
   double* d_lexp_vals = nullptr;
   size_t lexp_vals_cap = 0;
+  // Masked counts of the hit planes (gpe_hit_group_counts, hit_groups.h): a
+  // call's masks uint32[G][n_units], pad bits cleared, and its counts
+  // int32[n][G].  A caller's host matrix goes through d_lexb_in.
+  uint32_t* d_hitgrp_masks = nullptr;
+  size_t hitgrp_masks_cap = 0;
+  int32_t* d_hitgrp_out = nullptr;
+  size_t hitgrp_out_cap = 0;
+  float hitgrp_ms = 0;               // device events around the last call's kernel
   char* h_pin_vals = nullptr;        // pinned staging of gpe_run_values' copy back
   size_t h_pin_vals_cap = 0;
   float ms[3] = {0, 0, 0};

@@ -1885,7 +1885,8 @@ void gpe_destroy(gpe_ctx* ctx) {
                   ctx->d_inf_part, ctx->d_inf_idx, ctx->d_inf_dist, ctx->d_case_t,
                   ctx->d_lexp_vt, ctx->d_lexp_first, ctx->d_lexp_slot, ctx->d_lexp_ucase,
                   ctx->d_lexp_masks, ctx->d_lexp_counts, ctx->d_lexp_failed, ctx->d_lexp_cand,
-                  ctx->d_lexp_vals, ctx->d_jump_asm_typed_hits, ctx->d_lab_planes};
+                  ctx->d_lexp_vals, ctx->d_jump_asm_typed_hits, ctx->d_lab_planes,
+                  ctx->d_hitgrp_masks, ctx->d_hitgrp_out};
   if (ctx->comm && rccl().ok) (void)rccl().comm_destroy(ctx->comm);
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -2883,6 +2884,7 @@ int gpe_run_values_bits(gpe_ctx* ctx, uint32_t* out_planes) {
 #include "case_bits.h"
 #include "case_informed.h"
 #include "lexicase_par.h"
+#include "hit_groups.h"
 
 namespace {
 int moments_check(gpe_ctx* ctx) {

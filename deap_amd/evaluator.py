@@ -54,6 +54,7 @@ __all__ = ["SymbRegMSE", "SymbRegNumpySSE", "SymbRegSumSSE",
            "BooleanHits", "BooleanCaseHits",
            "exact_dd_sums", "check_case_subset",
            "TypedBoolHits", "TypedCaseHits", "GPUEvaluator", "gpu_map",
+           "TypedConfusion", "BooleanConfusion", "confusion_figures",
            "pack_bitplanes", "unpack_bitplanes", "plan_predict_chunks", "first_error_cases",
            "predict_error"]
 
@@ -683,6 +684,196 @@ class TypedCaseHits(TypedBoolHits):
         return out
 
 
+CONFUSION_NAMES = ("tp", "fp", "fn", "tn", "hits", "accuracy", "recall",
+                   "specificity", "precision", "balanced_accuracy", "f1",
+                   "mcc")
+
+
+def confusion_figures(conf, names=CONFUSION_NAMES):
+    """The class-aware figures of confusion counts ``int64[n, 4]`` in the
+    order tp, fp, fn, tn → ``{name: array[n]}`` for *names* (int64 for the
+    five counts, float64 for the rest).  With ``P = tp + fn`` and
+    ``N = fp + tn``, every operation an IEEE double one on the integers:
+
+    * ``hits = tp + tn``; ``accuracy = (tp + tn) / (P + N)``;
+    * ``recall = tp / P``, ``0.0`` when ``P == 0``;
+    * ``specificity = tn / N``, ``0.0`` when ``N == 0``;
+    * ``precision = tp / (tp + fp)``, ``0.0`` when that sum is 0;
+    * ``balanced_accuracy = (recall + specificity) / 2``; specificity alone
+      when ``P == 0``, recall alone when ``N == 0``;
+    * ``f1 = (2 * tp) / (2 * tp + fp + fn)``, ``0.0`` when the denominator
+      is 0;
+    * ``mcc = float(tp * tn - fp * fn) / (math.sqrt(float((tp + fp) *
+      (tp + fn))) * math.sqrt(float((tn + fp) * (tn + fn))))``, ``0.0`` when
+      either product is 0 (the products are exact integers: the counts are
+      below 2^31).
+
+    A row of ``-1`` (an individual that raised) gives figures without
+    meaning; the caller replaces them."""
+    conf = np.asarray(conf, dtype=np.int64).reshape(-1, 4)
+    tp, fp, fn, tn = conf[:, 0], conf[:, 1], conf[:, 2], conf[:, 3]
+    P, N = tp + fn, fp + tn
+    zeros = np.zeros(len(conf))
+    cols = {}
+    with np.errstate(all="ignore"):
+        def ratio(num, den):
+            return np.where(den == 0, zeros, num / den)
+        for name in names:
+            if name in cols:
+                continue
+            if name in ("tp", "fp", "fn", "tn"):
+                cols[name] = conf[:, ("tp", "fp", "fn", "tn").index(name)]
+            elif name == "hits":
+                cols[name] = tp + tn
+            elif name == "accuracy":
+                cols[name] = (tp + tn) / (P + N)
+            elif name == "recall":
+                cols[name] = ratio(tp, P)
+            elif name == "specificity":
+                cols[name] = ratio(tn, N)
+            elif name == "precision":
+                cols[name] = ratio(tp, tp + fp)
+            elif name == "balanced_accuracy":
+                rec, spe = ratio(tp, P), ratio(tn, N)
+                cols[name] = np.where(P == 0, spe,
+                                      np.where(N == 0, rec, (rec + spe) / 2))
+            elif name == "f1":
+                cols[name] = ratio(2 * tp, 2 * tp + fp + fn)
+            elif name == "mcc":
+                a, b = (tp + fp) * (tp + fn), (tn + fp) * (tn + fn)
+                num = (tp * tn - fp * fn).astype(np.float64)
+                den = np.sqrt(a.astype(np.float64)) * \
+                    np.sqrt(b.astype(np.float64))
+                cols[name] = np.where((a == 0) | (b == 0), zeros, num / den)
+            else:
+                raise ValueError("unknown confusion figure %r (the names are "
+                                 "%r)" % (name, CONFUSION_NAMES))
+    return cols
+
+
+class _Confusion(object):
+    """What :class:`TypedConfusion` and :class:`BooleanConfusion` share: the
+    *fitness* names, the confusion counts from the hits and the label-plane
+    count, and the vectorised fitness tuples."""
+    confusion = True
+    NAMES = CONFUSION_NAMES
+    cases = "device"
+
+    def _set_fitness(self, fitness):
+        if isinstance(fitness, str):
+            fitness = (fitness,)
+        fitness = tuple(fitness)
+        if not fitness or any(k not in self.NAMES for k in fitness):
+            raise ValueError("fitness must be a non-empty tuple drawn from "
+                             "%r (got %r)" % (self.NAMES, fitness))
+        self.fitness = fitness
+
+    def confusion_counts(self, hits, tp, err=None):
+        """``int64[n, 4]`` (tp, fp, fn, tn) from the hit counts, the hits on
+        the positive cases (the label plane's masked count) and the error
+        words; ``-1`` rows where the individual raised."""
+        hits = np.asarray(hits).astype(np.int64).reshape(-1)
+        tp = np.asarray(tp, dtype=np.int64).reshape(-1)
+        P = int(self.positives())
+        N = self.n_cases - P
+        tn = hits - tp
+        conf = np.stack([tp, N - tn, P - tp, tn], axis=1)
+        if err is not None:
+            conf[np.asarray(err) != np.uint64(_lib.GPE_NO_ERROR)] = -1
+        return conf
+
+    def finish(self, i, hi, lo, err, flags, cases=None):
+        return self.finish_all(np.asarray([hi]), None,
+                               None if err is None else
+                               np.asarray([err], dtype=np.uint64), None,
+                               cases=np.asarray([cases]).reshape(-1))[0]
+
+    def finish_all(self, hi, lo, err, flags, cases=None):
+        # (cases: the label plane's masked counts, the true positives)
+        if not len(hi):
+            return []
+        conf = self.confusion_counts(hi, cases, err)
+        cols = confusion_figures(conf, self.fitness)
+        out = list(zip(*[cols[k].tolist() for k in self.fitness]))
+        if err is not None:
+            for i in np.flatnonzero(err != np.uint64(_lib.GPE_NO_ERROR)).tolist():
+                out[i] = _case_error(err[i])
+        return out
+
+
+class TypedConfusion(_Confusion, TypedCaseHits):
+    """Class-aware fitness of a typed classifier (spambase.py) from the hit
+    planes :class:`TypedCaseHits` leaves on the GPU: after the hit-planes run
+    one masked count (``gpe_hit_group_counts`` with the label plane) gives
+    each individual's hits on the positive rows.  With ``P`` the number of
+    positive labels, ``N = n_cases - P`` and ``hits`` the count
+    :class:`TypedBoolHits` returns: ``tp`` is that count, ``tn = hits - tp``,
+    ``fn = P - tp``, ``fp = N - tn``.
+
+    *fitness* is a non-empty tuple drawn from ``"tp" "fp" "fn" "tn" "hits"``
+    (ints) and ``"accuracy" "recall" "specificity" "precision"
+    "balanced_accuracy" "f1" "mcc"`` (floats): the fitness tuple's entries in
+    that order, by the definitions of :func:`confusion_figures`:
+
+    * ``accuracy = (tp + tn) / (P + N)``
+    * ``recall = tp / P``, ``0.0`` when ``P == 0``
+    * ``specificity = tn / N``, ``0.0`` when ``N == 0``
+    * ``precision = tp / (tp + fp)``, ``0.0`` when that sum is 0
+    * ``balanced_accuracy = (recall + specificity) / 2``; when ``P == 0``
+      specificity alone, when ``N == 0`` recall alone
+    * ``f1 = (2 * tp) / (2 * tp + fp + fn)``, ``0.0`` when the denominator
+      is 0
+    * ``mcc = float(tp * tn - fp * fn) / (math.sqrt(float((tp + fp) *
+      (tp + fn))) * math.sqrt(float((tn + fp) * (tn + fn))))``, ``0.0`` when
+      either product is 0
+
+    each an IEEE double operation on Python ints.  There is no *cases*
+    argument: the matrix stays on the GPU as with ``cases="device"``, and
+    :meth:`GPUEvaluator.select_lexicase` (every mode, *parallel* too),
+    :meth:`GPUEvaluator.informed_subsample`, :meth:`GPUEvaluator.subsample`,
+    :meth:`GPUEvaluator.last_case_hits`, :meth:`GPUEvaluator.group_hits` and
+    ``last_hits`` work as for :class:`TypedCaseHits`.
+    ``GPUEvaluator.last_confusion`` is ``int64[n, 4]`` in the order tp, fp,
+    fn, tn (a row of ``-1`` where the individual raised).  Exceptions and
+    setup refusals are :class:`TypedCaseHits`'.  fp64, one GPU."""
+
+    def __init__(self, X, labels, fitness=("balanced_accuracy",)):
+        TypedCaseHits.__init__(self, X, labels, "device")
+        self._set_fitness(fitness)
+
+    def label_plane(self):
+        """``uint32[ceil(n_cases / 32)]``: bit c set where label c is true."""
+        return pack_bitplanes(self.labels[0] != 0)[0]
+
+    def positives(self):
+        return int(np.count_nonzero(self.labels[0]))
+
+
+class BooleanConfusion(_Confusion, BooleanCaseHits):
+    """:class:`TypedConfusion`'s figures for a boolean problem (the positive
+    cases are those whose output is 1), from :class:`BooleanCaseHits`' hit
+    planes and one masked count with the output plane.  *fitness*, the
+    definitions, ``last_confusion`` and what keeps working are
+    :class:`TypedConfusion`'s; validation, :meth:`from_rows` and the refusal
+    of typed primitive sets are :class:`BooleanCaseHits`'."""
+
+    def __init__(self, inputs, outputs, fitness=("balanced_accuracy",)):
+        BooleanCaseHits.__init__(self, inputs, outputs, "device")
+        self._set_fitness(fitness)
+
+    @classmethod
+    def from_rows(cls, inputs, outputs, fitness=("balanced_accuracy",)):
+        """Reference layout: ``inputs[case][var]``, ``outputs[case]``."""
+        return cls(np.asarray(inputs).T, np.asarray(outputs), fitness)
+
+    def label_plane(self):
+        """``uint32[ceil(n_cases / 32)]``: bit c set where output c is 1."""
+        return self.out_plane
+
+    def positives(self):
+        return int(unpack_bitplanes(self.out_plane, self.n_cases).sum())
+
+
 # ------------------------------------------------------------- evaluator --
 def trig_leaf_columns(pset_spec, spec, precision="fp64"):
     """Argument indices whose sin/cos leaves may be read from device columns:
@@ -832,6 +1023,8 @@ class GPUEvaluator(object):
         self.last_mae = np.zeros(0)
         self.last_max_error = np.zeros(0)
         self.last_hits = np.zeros(0, dtype=np.int64)
+        # TypedConfusion / BooleanConfusion: (tp, fp, fn, tn) per individual
+        self.last_confusion = np.zeros((0, 4), dtype=np.int64)
         # select_lexicase: the individuals (kept, so that their identities
         # stay theirs) and results of the last evaluation that left a
         # per-case matrix on the GPU
@@ -1226,6 +1419,16 @@ class GPUEvaluator(object):
                 cases, hi = self.ctx.run_hit_planes(
                     want_planes=self.spec.cases == "host")
             self.last_hits = np.asarray(hi).astype(np.int64)
+            if getattr(self.spec, "confusion", False):
+                # (the true positives in cases' place: one masked count of
+                # the resident planes with the active spec's label plane)
+                cases = self.ctx.hit_group_counts(
+                    None, 0, 0, self.spec.label_plane()[None, :])[:, 0] \
+                    if len(self.last_hits) else np.zeros(0, dtype=np.int64)
+                conf = self.spec.confusion_counts(hi, cases, err)
+                if getattr(batch, "any_err", True):
+                    conf[np.flatnonzero(batch.err)] = -1
+                self.last_confusion = conf
         elif getattr(self.spec, "per_case", False):
             cases, hi, lo, err, flags = self.ctx.run_cases(
                 self.spec.mode, self.spec.n_cases)
@@ -1415,6 +1618,85 @@ class GPUEvaluator(object):
         if n == 0:
             return np.zeros((0, self.spec.n_cases), dtype=bool)
         return unpack_bitplanes(self.ctx.hit_planes(n), self.spec.n_cases)
+
+    def _group_masks(self, groups):
+        """*groups* of :meth:`group_hits` as ``bool[G, n_cases]``."""
+        n_cases = self.spec.n_cases
+        arr = groups if isinstance(groups, np.ndarray) else None
+        if arr is None:
+            try:
+                arr = np.asarray(groups)
+            except ValueError:          # (ragged index lists)
+                arr = None
+        if arr is not None and arr.dtype == bool and arr.ndim == 2:
+            if arr.shape[1] != n_cases:
+                raise ValueError("group_hits: a boolean groups array must be "
+                                 "[G, %d] (got %r)" % (n_cases, arr.shape))
+            return arr
+        masks = np.zeros((len(groups), n_cases), dtype=bool)
+        for g, members in enumerate(groups):
+            a = np.asarray(members)
+            if a.size == 0:
+                continue
+            if a.ndim != 1 or a.dtype.kind not in "iu":
+                raise ValueError("group_hits: groups[%d] must be a 1-D "
+                                 "sequence of integer case indices" % g)
+            bad = np.flatnonzero((a < 0) | (a >= n_cases))
+            if len(bad):
+                raise IndexError("group_hits: groups[%d][%d] = %d is outside "
+                                 "[0, %d)" % (g, bad[0], a[bad[0]], n_cases))
+            masks[g, a] = True
+        return masks
+
+    def group_hits(self, groups):
+        """``int64[n, G]``: each individual's hits inside each of *G* case
+        groups, counted on the GPU from the hit matrix the last
+        :meth:`evaluate` / :meth:`map` left there (``gpe_hit_group_counts``;
+        :class:`BooleanCaseHits`, :class:`TypedCaseHits`,
+        :class:`BooleanConfusion` or :class:`TypedConfusion`, either *cases*
+        mode): per-fold, per-stratum or train / validation counts from one
+        evaluation, with no ``n x n_cases`` copy.
+
+        *groups*: ``bool[G, n_cases]``, or a sequence of *G* integer index
+        sequences over the active cases (positions in ``case_subset`` while a
+        subset is active, as first-error cases are); duplicates inside a
+        group count once, an index out of range raises ``IndexError`` (a
+        negative one included).  More than 8 groups are counted in slices of
+        8.  An individual whose result is an exception gets a row of ``-1``.
+        ``ValueError`` when the last evaluate / map left no hit planes (as
+        :meth:`last_case_hits`) or another batch has been loaded since (as
+        :meth:`select_lexicase`)."""
+        if not getattr(self.spec, "hit_planes", False) or \
+                self._lex_batch is None:
+            raise ValueError(
+                "group_hits: this evaluator's last evaluate / map left "
+                "no hit planes on the GPU (its spec is %s; evaluate with "
+                "BooleanCaseHits, TypedCaseHits, BooleanConfusion or "
+                "TypedConfusion first)" % type(self.spec).__name__)
+        last, results = self._lex_batch
+        if self.ctx.n_prog != len(last):
+            raise ValueError(
+                "group_hits: the context now holds %d programs, not the "
+                "%d of the last evaluate / map; evaluate the batch again"
+                % (self.ctx.n_prog, len(last)))
+        masks = self._group_masks(groups)
+        n, G = len(last), len(masks)
+        out = np.zeros((n, G), dtype=np.int64)
+        if n == 0 or G == 0:
+            return out
+        planes = pack_bitplanes(masks)
+        for s in range(0, G, _lib.HIT_GROUPS_MAX):
+            e = min(G, s + _lib.HIT_GROUPS_MAX)
+            out[:, s:e] = self.ctx.hit_group_counts(None, 0, 0, planes[s:e])
+        # (who raised: found once per evaluation, a pass over a million
+        # results costs more than the count)
+        cache = getattr(self, "_group_raised", None)
+        if cache is None or cache[0] is not results:
+            cache = self._group_raised = (results, [
+                i for i, res in enumerate(results)
+                if isinstance(res, BaseException)])
+        out[cache[1]] = -1
+        return out
 
     def map(self, individuals):
         return _yield_until_error(self.evaluate(list(individuals)))

@@ -521,6 +521,42 @@ int gpe_host_lexicase_par(const double* values, int64_t n, int64_t n_cases,
  * keeps in LDS; larger candidate sets go through device scratch. */
 int64_t gpe_lexicase_par_lds_values(void);
 
+/* Masked counts of a hit matrix: out[i][g] = popcount(row_i & mask_g), an
+ * individual's hits inside each of G case groups.  With the label plane as
+ * the one mask the count is a classifier's true positives (and hits - tp its
+ * true negatives); with fold, stratum or train / validation planes one
+ * evaluation gives every group's count.  planes is a HOST program-major hit
+ * matrix uint32[n][ceil(n_cases / 32)] (gpe_run_hit_planes' layout: case c at
+ * bit c % 32 of word c / 32), or NULL for the resident matrix of the loaded
+ * programs (the last gpe_run_hit_planes / gpe_run_typed_hit_planes; n and
+ * n_cases are then the context's, GPE_E_STATE as gpe_lexicase_bits_par(NULL)
+ * when none is valid or the program count differs).  masks is a HOST
+ * uint32[G][ceil(n_cases / 32)] of the same layout, 1 <= G <= 8, copied to
+ * the device per call (G * n_units words; not a case upload).  The library
+ * clears the masks' pad bits itself, so a caller's planes may carry set pad
+ * bits and a mask with pad bits set counts as the same mask without them.
+ * out is a HOST int32[n][G].  GPE_E_ARG with a message for G outside 1 .. 8,
+ * n < 0, n_cases outside 1 .. 2^31 - 1 with explicit planes, a NULL masks, or
+ * a NULL out with n > 0; n == 0 succeeds and writes nothing.  Rows of up to
+ * 64 words get a power-of-two group of lanes each (several rows a wave),
+ * longer ones a whole wave per four rows; no atomics.  The call disturbs
+ * nothing else: the counts, the resident fitness, the hit planes and their
+ * transpose, and the active case set stay as they were. */
+int gpe_hit_group_counts(gpe_ctx* ctx, const uint32_t* planes, int64_t n,
+                         int64_t n_cases, const uint32_t* masks, int G,
+                         int32_t* out);
+
+/* Device time of the last gpe_hit_group_counts' kernel in ms (events around
+ * the launch; the copies of the masks and the counts are outside). */
+int gpe_last_hit_group_ms(const gpe_ctx* ctx, float* ms);
+
+/* Host twin of gpe_hit_group_counts on a host matrix (no GPU): the same
+ * arithmetic in plain C++; GPE_E_ARG for the arguments it refuses and for a
+ * NULL planes with n > 0. */
+int gpe_host_hit_group_counts(const uint32_t* planes, int64_t n,
+                              int64_t n_cases, const uint32_t* masks, int G,
+                              int32_t* out);
+
 /* Device tournament selection that replays the reference's random stream:
  * selTournament (deap/tools/selection.py:51-69, aspirants drawn by selRandom
  * :15-28, i.e. random.choice) — k tournaments of tournsize aspirants, the
