@@ -5,6 +5,7 @@ The library is built in-tree by ``__graft_entry__.build()`` /
 missing or fails to load, every evaluator entry point raises.
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -88,6 +89,16 @@ SIGNATURES = {
     "gpe_hit_group_counts": (_I, [_P, _P, _I64, _I64, _P, _I, _P]),
     "gpe_host_hit_group_counts": (_I, [_P, _I64, _I64, _P, _I, _P]),
     "gpe_last_hit_group_ms": (_I, [_P, ctypes.POINTER(ctypes.c_float)]),
+    "gpe_case_solve_counts": (_I, [_P, _P, _I64, _I64, ctypes.c_double, _P,
+                                   _P]),
+    "gpe_hit_weighted_sums": (_I, [_P, _P, _I64, _I64, ctypes.c_double, _P,
+                                   _I, _P]),
+    "gpe_hit_shared_sums": (_I, [_P, _P, _I64, _I64, ctypes.c_double, _P, _P,
+                                 _P]),
+    "gpe_last_case_weights_ms": (_I, [_P, ctypes.POINTER(ctypes.c_float)]),
+    "gpe_host_case_solve_counts": (_I, [_P, _I64, _I64, _P, _P]),
+    "gpe_host_hit_weighted_sums": (_I, [_P, _I64, _I64, _P, _I, _P, _P]),
+    "gpe_host_hit_shared_sums": (_I, [_P, _I64, _I64, _P, _P, _P, _P]),
     "gpe_set_lowering": (_I, [_P, _I, _I, _P, _I, _P, _I]),
     "gpe_lower_programs": (_I, [_P, _P, _P, _I64, _P, _P, _P, _P, _P]),
     "gpe_lower_begin": (_I, [_P, _I64]),
@@ -367,6 +378,114 @@ def host_hit_group_counts(planes, n_cases, masks):
     if rc != 0:
         raise GpeError("gpe_host_hit_group_counts failed (%d)" % rc)
     return out[:, :G].astype(np.int64)
+
+
+HIT_WEIGHTS_MAX = 8
+
+
+def check_case_weights(what, weights, n_cases):
+    """The weights of a weighted-hits call as float64 ``[G, n_cases]``
+    (``-0.0`` as ``0.0``): 1-D or 2-D, every weight finite and ``>= 0``,
+    ``math.fsum`` of every row finite; ``ValueError`` otherwise."""
+    try:
+        w = np.array(weights, dtype=np.float64, order="C", ndmin=2)
+    except (TypeError, ValueError):
+        raise ValueError("%s: weights must be a float array [n_cases] or "
+                         "[G, n_cases]" % what)
+    if w.ndim != 2 or w.shape[1] != int(n_cases):
+        raise ValueError("%s: weights must be float64 [%d] or [G, %d] (got "
+                         "shape %r)" % (what, n_cases, n_cases,
+                                        np.shape(weights)))
+    if not np.isfinite(w).all():
+        raise ValueError("%s: every weight must be finite (got a nan or an "
+                         "inf)" % what)
+    if (w < 0.0).any():
+        raise ValueError("%s: every weight must be >= 0 (got %r)"
+                         % (what, float(w[w < 0.0][0])))
+    w += 0.0                                      # (-0.0 + 0.0 is +0.0)
+    for g in range(w.shape[0]):
+        # (fsum only where the sum can be near the top of the range)
+        if float(w[g].max(initial=0.0)) * w.shape[1] >= 1e308:
+            try:
+                total = math.fsum(w[g].tolist())
+            except OverflowError:
+                total = math.inf
+            if not math.isfinite(total):
+                raise ValueError("%s: the sum of weights[%d] overflows a "
+                                 "float" % (what, g))
+    return w
+
+
+def pack_live_mask(live):
+    """``bool[n]`` → uint64 ``[ceil(n / 64)]``, individual i at bit i % 64 of
+    word i / 64 (the live mask of the solve counts)."""
+    live = np.ascontiguousarray(live, dtype=bool)
+    by = np.packbits(live, bitorder="little")
+    out = np.zeros((len(live) + 63) // 64 * 8, dtype=np.uint8)
+    out[:len(by)] = by
+    return out.view("<u8").astype(np.uint64)
+
+
+def _check_live(what, live, n):
+    if live is None:
+        return None
+    live = np.ascontiguousarray(live, dtype=np.uint64)
+    if live.shape != ((int(n) + 63) // 64,):
+        raise ValueError("%s: live must be uint64 [%d] for %d individuals"
+                         % (what, (int(n) + 63) // 64, n))
+    return live
+
+
+def host_case_solve_counts(planes, n_cases, live=None):
+    """Host twin of :meth:`Context.case_solve_counts` (CPU, no GPU): a
+    program-major hit matrix ``uint32[n, ceil(n_cases / 32)]`` and an
+    optional live mask ``uint64[ceil(n / 64)]`` → ``int64[n_cases]``."""
+    planes = _check_planes("host_case_solve_counts", planes, n_cases)
+    n = planes.shape[0]
+    live = _check_live("host_case_solve_counts", live, n)
+    out = np.zeros(int(n_cases), dtype=np.int32)
+    rc = load().gpe_host_case_solve_counts(
+        _ptr(planes) if n else None, n, int(n_cases), _ptr(live), _ptr(out))
+    if rc != 0:
+        raise GpeError("gpe_host_case_solve_counts failed (%d)" % rc)
+    return out.astype(np.int64)
+
+
+def host_hit_weighted_sums(planes, n_cases, weights, pair=False):
+    """Host twin of :meth:`Context.hit_weighted_sums` (CPU, no GPU): the
+    same double-double sum in the same order → ``float64[n, G]``; with
+    *pair* ``(hi, lo)``, the final normalised pair."""
+    planes = _check_planes("host_hit_weighted_sums", planes, n_cases)
+    w = check_case_weights("host_hit_weighted_sums", weights, n_cases)
+    n, G = planes.shape[0], w.shape[0]
+    hi = np.zeros((max(n, 1), max(G, 1)), dtype=np.float64)
+    lo = np.zeros_like(hi)
+    rc = load().gpe_host_hit_weighted_sums(
+        _ptr(planes) if n else None, n, int(n_cases), _ptr(w), G,
+        _ptr(hi), _ptr(lo))
+    if rc != 0:
+        raise GpeError("gpe_host_hit_weighted_sums failed (%d)" % rc)
+    hi, lo = hi[:n, :G], lo[:n, :G]
+    return (hi, lo) if pair else hi
+
+
+def host_hit_shared_sums(planes, n_cases, live=None, pair=False):
+    """Host twin of :meth:`Context.hit_shared_sums` (CPU, no GPU) →
+    ``(counts int64[n_cases], sums float64[n])``; with *pair* the sums are
+    ``(hi, lo)``."""
+    planes = _check_planes("host_hit_shared_sums", planes, n_cases)
+    n = planes.shape[0]
+    live = _check_live("host_hit_shared_sums", live, n)
+    cnt = np.zeros(int(n_cases), dtype=np.int32)
+    hi = np.zeros(max(n, 1), dtype=np.float64)
+    lo = np.zeros_like(hi)
+    rc = load().gpe_host_hit_shared_sums(
+        _ptr(planes) if n else None, n, int(n_cases), _ptr(live), _ptr(cnt),
+        _ptr(hi), _ptr(lo))
+    if rc != 0:
+        raise GpeError("gpe_host_hit_shared_sums failed (%d)" % rc)
+    hi, lo = hi[:n], lo[:n]
+    return cnt.astype(np.int64), ((hi, lo) if pair else hi)
 
 
 def lexicase_par_lds_values():
@@ -1100,6 +1219,76 @@ class Context(object):
         ms = ctypes.c_float(0.0)
         self._check(self.lib.gpe_last_hit_group_ms(self.h, ctypes.byref(ms)),
                     "gpe_last_hit_group_ms")
+        return float(ms.value)
+
+    def _weights_matrix(self, what, planes, n, n_cases):
+        """The matrix argument of the case-weight calls →
+        ``(rows, n, n_cases, cases, ptr, keep)``: *rows* / *cases* the shape
+        the outputs need, *n* / *n_cases* / *ptr* the library's arguments."""
+        if planes is None:
+            return self.n_prog, 0, 0, self.n_cases, None, None
+        planes = _check_planes(what, planes, n_cases)
+        if planes.shape[0] != int(n):
+            raise ValueError("%s: planes must be uint32 [%d, %d]"
+                             % (what, n, planes.shape[1]))
+        # (a matrix of no rows is still the caller's, not the resident one)
+        keep = planes if planes.size else np.zeros(1, dtype=np.uint32)
+        return int(n), int(n), int(n_cases), int(n_cases), _ptr(keep), keep
+
+    def case_solve_counts(self, planes, n, n_cases, eps=0.0, live=None):
+        """gpe_case_solve_counts → ``int64[n_cases]``: the live individuals
+        that hit each case.  *planes*: a program-major hit matrix uint32
+        [n, ceil(n_cases / 32)], or None for the resident matrix of the
+        loaded programs (*n*, *n_cases* are then the context's; *eps*
+        thresholds the F machine's per-case matrix, as
+        :meth:`informed_cases`).  *live*: uint64 [ceil(n / 64)]
+        (:func:`pack_live_mask`) or None.  Nothing resident is disturbed."""
+        rows, n, n_cases, cases, ptr, keep = self._weights_matrix(
+            "case_solve_counts", planes, n, n_cases)
+        live = _check_live("case_solve_counts", live, rows)
+        out = np.zeros(max(cases, 1), dtype=np.int32)
+        self._check(self.lib.gpe_case_solve_counts(
+            self.h, ptr, n, n_cases, float(eps), _ptr(live), _ptr(out)),
+            "gpe_case_solve_counts")
+        return out[:cases].astype(np.int64)
+
+    def hit_weighted_sums(self, planes, n, n_cases, weights, eps=0.0):
+        """gpe_hit_weighted_sums → ``float64[n, G]``: every program's sum of
+        ``weights[g]`` over the cases it hits, *weights* float64
+        ``[G, n_cases]`` (or 1-D), *G* in 1 .. 8, checked by
+        :func:`check_case_weights`.  The matrix as
+        :meth:`case_solve_counts`."""
+        rows, n, n_cases, cases, ptr, keep = self._weights_matrix(
+            "hit_weighted_sums", planes, n, n_cases)
+        w = check_case_weights("hit_weighted_sums", weights, cases)
+        G = w.shape[0]
+        out = np.zeros((max(rows, 1), max(G, 1)), dtype=np.float64)
+        self._check(self.lib.gpe_hit_weighted_sums(
+            self.h, ptr, n, n_cases, float(eps), _ptr(w), G, _ptr(out)),
+            "gpe_hit_weighted_sums")
+        return out[:rows, :G]
+
+    def hit_shared_sums(self, planes, n, n_cases, eps=0.0, live=None):
+        """gpe_hit_shared_sums → ``(counts int64[n_cases], sums
+        float64[n])``: the solve counts over the *live* individuals and every
+        program's sum of ``1 / counts[c]`` over the cases it hits (implicit
+        fitness sharing), the weights made on the device.  The matrix and
+        *live* as :meth:`case_solve_counts`."""
+        rows, n, n_cases, cases, ptr, keep = self._weights_matrix(
+            "hit_shared_sums", planes, n, n_cases)
+        live = _check_live("hit_shared_sums", live, rows)
+        cnt = np.zeros(max(cases, 1), dtype=np.int32)
+        out = np.zeros(max(rows, 1), dtype=np.float64)
+        self._check(self.lib.gpe_hit_shared_sums(
+            self.h, ptr, n, n_cases, float(eps), _ptr(live), _ptr(cnt),
+            _ptr(out)), "gpe_hit_shared_sums")
+        return cnt[:cases].astype(np.int64), out[:rows]
+
+    def case_weights_ms(self):
+        """Device ms of the last case-weight call's kernels."""
+        ms = ctypes.c_float(0.0)
+        self._check(self.lib.gpe_last_case_weights_ms(self.h, ctypes.byref(ms)),
+                    "gpe_last_case_weights_ms")
         return float(ms.value)
 
     def informed_cases(self, planes, n, n_cases, eps, seed, m):

@@ -585,6 +585,20 @@ struct gpe_ctx {
   int32_t* d_hitgrp_out = nullptr;
   size_t hitgrp_out_cap = 0;
   float hitgrp_ms = 0;               // device events around the last call's kernel
+  // Case weights on the hit planes (gpe_case_solve_counts,
+  // gpe_hit_weighted_sums, gpe_hit_shared_sums; hit_weights.h): a call's
+  // weights double[G][n_cases] (or the sharing weights the counts kernel
+  // writes), its sums double[n][G], the solve counts int32[n_cases] and the
+  // live mask uint64[ceil(n / 64)].
+  double* d_hw_w = nullptr;
+  size_t hw_w_cap = 0;
+  double* d_hw_out = nullptr;
+  size_t hw_out_cap = 0;
+  int32_t* d_hw_cnt = nullptr;
+  size_t hw_cnt_cap = 0;
+  unsigned long long* d_hw_live = nullptr;
+  size_t hw_live_cap = 0;
+  float hw_ms = 0;                   // device events around the last call's kernels
   char* h_pin_vals = nullptr;        // pinned staging of gpe_run_values' copy back
   size_t h_pin_vals_cap = 0;
   float ms[3] = {0, 0, 0};

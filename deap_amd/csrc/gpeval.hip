@@ -1886,7 +1886,8 @@ void gpe_destroy(gpe_ctx* ctx) {
                   ctx->d_lexp_vt, ctx->d_lexp_first, ctx->d_lexp_slot, ctx->d_lexp_ucase,
                   ctx->d_lexp_masks, ctx->d_lexp_counts, ctx->d_lexp_failed, ctx->d_lexp_cand,
                   ctx->d_lexp_vals, ctx->d_jump_asm_typed_hits, ctx->d_lab_planes,
-                  ctx->d_hitgrp_masks, ctx->d_hitgrp_out};
+                  ctx->d_hitgrp_masks, ctx->d_hitgrp_out, ctx->d_hw_w, ctx->d_hw_out,
+                  ctx->d_hw_cnt, ctx->d_hw_live};
   if (ctx->comm && rccl().ok) (void)rccl().comm_destroy(ctx->comm);
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -2885,6 +2886,7 @@ int gpe_run_values_bits(gpe_ctx* ctx, uint32_t* out_planes) {
 #include "case_informed.h"
 #include "lexicase_par.h"
 #include "hit_groups.h"
+#include "hit_weights.h"
 
 namespace {
 int moments_check(gpe_ctx* ctx) {

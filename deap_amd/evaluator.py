@@ -1033,6 +1033,8 @@ class GPUEvaluator(object):
         self.last_lexicase_seed = None
         # informed_subsample: each pick's distance to the nearest earlier one
         self.last_informed_distances = np.zeros(0, dtype=np.int32)
+        # shared_hits: how many individuals solve each case
+        self.last_solve_counts = np.zeros(0, dtype=np.int64)
 
     def close(self):
         """Release the device contexts (the evaluator's and predict's)."""
@@ -1696,6 +1698,115 @@ class GPUEvaluator(object):
                 i for i, res in enumerate(results)
                 if isinstance(res, BaseException)])
         out[cache[1]] = -1
+        return out
+
+    def _case_weights_batch(self, what, eps):
+        """The checks the case-weight calls share → ``(n, eps, raised,
+        live)``: the batch's size, the threshold to pass on, the indices of
+        the individuals whose result is an exception and the live mask
+        (None when nobody raised)."""
+        bits = getattr(self.spec, "hit_planes", False)
+        if self._lex_batch is None or \
+                not (bits or getattr(self.spec, "abs_cases", False)):
+            raise ValueError(
+                "%s: this evaluator's last evaluate / map left no hit planes "
+                "and no per-case absolute errors on the GPU (its spec is %s; "
+                "evaluate with BooleanCaseHits, TypedCaseHits, "
+                "BooleanConfusion, TypedConfusion or SymbRegCaseAbsErrors "
+                "first)" % (what, type(self.spec).__name__))
+        if bits and eps is not None:
+            raise ValueError("%s: eps applies to SymbRegCaseAbsErrors; the "
+                             "cases of %s are hits already (got eps=%r)"
+                             % (what, type(self.spec).__name__, eps))
+        last, results = self._lex_batch
+        if self.ctx.n_prog != len(last):
+            raise ValueError(
+                "%s: the context now holds %d programs, not the "
+                "%d of the last evaluate / map; evaluate the batch again"
+                % (what, self.ctx.n_prog, len(last)))
+        if bits:
+            eps = 0.0
+        else:
+            eps = self.spec.hit_eps if eps is None else float(eps)
+            if not eps >= 0.0:
+                raise ValueError("%s: eps must be >= 0 (got %r)" % (what, eps))
+        cache = getattr(self, "_group_raised", None)
+        if cache is None or cache[0] is not results:
+            cache = self._group_raised = (results, [
+                i for i, res in enumerate(results)
+                if isinstance(res, BaseException)])
+        live = None
+        if cache[1]:
+            alive = np.ones(len(last), dtype=bool)
+            alive[cache[1]] = False
+            live = _lib.pack_live_mask(alive)
+        return len(last), eps, cache[1], live
+
+    def case_solve_counts(self, eps=None):
+        """``int64[n_cases]``: how many individuals of the last
+        :meth:`evaluate` / :meth:`map` solve each case, counted on the GPU
+        from the per-case matrix that evaluation left there
+        (``gpe_case_solve_counts``): the hit planes of
+        :class:`BooleanCaseHits`, :class:`TypedCaseHits`,
+        :class:`BooleanConfusion` or :class:`TypedConfusion`, or
+        :class:`SymbRegCaseAbsErrors`' absolute errors, where a case is
+        solved when its error is finite and ``<= eps`` (default
+        ``spec.hit_eps``; *eps* with a hit-plane spec is a ``ValueError``).
+        An individual whose result is an exception is not counted.  While a
+        case subset is active the positions are those of the active cases.
+        Nothing is drawn from ``random`` and nothing resident changes.
+        ``ValueError`` when the last evaluate / map left no such matrix or
+        another batch has been loaded since (as :meth:`group_hits`)."""
+        n, eps, _, live = self._case_weights_batch("case_solve_counts", eps)
+        if n == 0:
+            return np.zeros(self.spec.n_cases, dtype=np.int64)
+        return self.ctx.case_solve_counts(None, 0, 0, eps, live)
+
+    def weighted_hits(self, weights, eps=None):
+        """Each individual's sum of *weights* over the cases it solves
+        (``gpe_hit_weighted_sums``): ``float64[n]`` for 1-D *weights*
+        ``[n_cases]``, ``float64[n, G]`` for 2-D ``[G, n_cases]`` (one column
+        per boosting round, fold or cost vector; more than 8 rows go in slices
+        of 8).  The matrix, *eps* and the ``ValueError`` s of the batch are
+        :meth:`case_solve_counts`'.  Every weight must be finite and ``>= 0``
+        (``-0.0`` is ``0.0``) and ``math.fsum`` of every row finite, else
+        ``ValueError`` before the GPU is touched.  The sum is a
+        double-double sum in one fixed order: within 1e-12
+        relative of ``math.fsum``, equal to it whenever the partial sums are
+        representable; no hits give ``+0.0``.  An individual whose result is
+        an exception gets ``nan`` (where :meth:`group_hits` gives -1)."""
+        n, eps, raised, _ = self._case_weights_batch("weighted_hits", eps)
+        one = np.ndim(weights) == 1
+        w = _lib.check_case_weights("weighted_hits", weights,
+                                    self.spec.n_cases)
+        G = w.shape[0]
+        out = np.zeros((n, G), dtype=np.float64)
+        if n and G:
+            for s in range(0, G, _lib.HIT_WEIGHTS_MAX):
+                e = min(G, s + _lib.HIT_WEIGHTS_MAX)
+                out[:, s:e] = self.ctx.hit_weighted_sums(None, 0, 0, w[s:e],
+                                                         eps)
+            out[raised] = np.nan
+        return out[:, 0] if one else out
+
+    def shared_hits(self, eps=None):
+        """``float64[n]``: implicit fitness sharing (Smith et al. 1993;
+        McKay 2000) — a case is worth ``1 / (the number of individuals that
+        solve it)`` and an individual's value is the sum of the worth of the
+        cases it solves (``gpe_hit_shared_sums``: counts, weights and sums
+        stay on the GPU).  ``last_solve_counts`` (``int64[n_cases]``) holds
+        the counts.  The matrix, *eps*, the accuracy and the ``ValueError`` s
+        are :meth:`weighted_hits`'; an individual whose result is an
+        exception is left out of the counts and gets ``nan``."""
+        n, eps, raised, live = self._case_weights_batch("shared_hits", eps)
+        if n == 0:
+            self.last_solve_counts = np.zeros(self.spec.n_cases,
+                                              dtype=np.int64)
+            return np.zeros(0, dtype=np.float64)
+        self.last_solve_counts, out = self.ctx.hit_shared_sums(
+            None, 0, 0, eps, live)
+        out = np.array(out)
+        out[raised] = np.nan
         return out
 
     def map(self, individuals):

@@ -557,6 +557,85 @@ int gpe_host_hit_group_counts(const uint32_t* planes, int64_t n,
                               int64_t n_cases, const uint32_t* masks, int G,
                               int32_t* out);
 
+/* Case weights on a hit matrix H (bool[n][n_cases]): three entry points that
+ * share their matrix argument.  planes is a HOST program-major hit matrix
+ * uint32[n][ceil(n_cases / 32)] (eps is ignored; set pad bits are ignored
+ * too), or NULL for the resident matrix of the loaded programs by
+ * gpe_informed_cases' routes (n, n_cases are then the context's): the hit
+ * planes of the last gpe_run_hit_planes / gpe_run_typed_hit_planes, or on the
+ * F machine without them the per-case matrix of the last gpe_run_abserr_cases
+ * / gpe_run_cases, where case c is a hit of program i when its value e is
+ * finite and e <= eps (eps >= 0 and not nan, else GPE_E_ARG).  GPE_E_STATE
+ * with gpe_informed_cases' messages when no such matrix of the loaded
+ * programs is resident.  GPE_E_ARG with a message naming the value for n < 0,
+ * n_cases outside 1 .. 2^31 - 1, and for n > INT32_MAX where counts are made;
+ * n == 0 succeeds (explicit planes: the counts are written as zeros, no sum
+ * is).  Nothing resident is written except the cached case-major transpose
+ * of the hit planes (gpe_lexicase_bits' d_hit_t): the per-case matrix, the hit
+ * planes, the resident fitness, the active case set and every launch plan
+ * stay as they were.
+ *
+ * gpe_case_solve_counts: out_counts int32[n_cases] (HOST, not NULL),
+ * s[c] = the programs i with H[i][c] and live bit i set.  live is a HOST
+ * uint64[ceil(n / 64)], program i at bit i % 64 of word i / 64 (bits past n
+ * are ignored), or NULL for all live.  A popcount of the case-major planes:
+ * a power-of-two group of lanes per case (a whole wave from 4,033 programs
+ * on), integer shuffles, no atomics. */
+int gpe_case_solve_counts(gpe_ctx* ctx, const uint32_t* planes, int64_t n,
+                          int64_t n_cases, double eps, const uint64_t* live,
+                          int32_t* out_counts);
+
+/* Weighted hits: out[i][g] = the sum of weights[g][c] over the cases c with
+ * H[i][c]; weights is a HOST double[G][n_cases], 1 <= G <= 8, every weight
+ * finite and >= 0 (-0.0 counts as 0.0) and every row's sum finite (the caller
+ * checks the sum); out is a HOST double[n][G].  A row with no hits is +0.0.
+ * The sum is a double-double sum in one fixed order, whatever G, the row
+ * length and the grid are: partial p of 64 takes the hit cases c = p, p + 64,
+ * ... in ascending order by (hi, r) = two_sum(hi, w); lo += r; the partials
+ * merge by the xor butterfly m = 32 .. 1, partial p taking
+ * dd_add(partial p, partial p ^ m) (gpe_run_abserr's dd_add); out is hi of
+ * partial 0.  With non-negative terms nothing cancels: |hi + lo - S| <=
+ * n_cases * 2^-100 * S for the exact sum S, so out is S rounded to fp64 or
+ * its neighbour, and exactly S whenever every partial sum is representable.
+ * A wave per row; the weights sit in LDS while G * n_cases * 8 bytes fit
+ * 64 KiB and are read through L2 otherwise, with the same bits.  GPE_E_ARG
+ * with a message for G outside 1 .. 8, a NULL weights, a NULL out with n > 0,
+ * and a weight that is negative, nan or inf. */
+int gpe_hit_weighted_sums(gpe_ctx* ctx, const uint32_t* planes, int64_t n,
+                          int64_t n_cases, double eps, const double* weights,
+                          int G, double* out);
+
+/* Implicit fitness sharing: gpe_case_solve_counts (live, out_counts as there;
+ * out_counts may be NULL), then gpe_hit_weighted_sums with G = 1 under
+ * w[c] = s[c] > 0 ? 1.0 / (double)s[c] : 0.0 (one correctly rounded
+ * division), out a HOST double[n].  The counts kernel writes the weights on
+ * the device and the sums kernel follows it on the stream: neither the counts
+ * nor the weights visit the host in between.  A program whose live bit is
+ * clear is left out of the counts; its own sum is still written (the caller
+ * overwrites it). */
+int gpe_hit_shared_sums(gpe_ctx* ctx, const uint32_t* planes, int64_t n,
+                        int64_t n_cases, double eps, const uint64_t* live,
+                        int32_t* out_counts, double* out);
+
+/* Device time of the last of these three calls' kernels in ms (events around
+ * the counts and sums launches; the copies, the thresholding and the
+ * transposition are outside). */
+int gpe_last_case_weights_ms(const gpe_ctx* ctx, float* ms);
+
+/* Host twins on a host matrix (no GPU): plain loops in the same order, so
+ * the sums agree bit for bit.  out_lo (may be NULL) receives lo of the final
+ * normalised pair, for accuracy tests.  GPE_E_ARG for the arguments the device
+ * calls refuse and for a NULL planes with n > 0. */
+int gpe_host_case_solve_counts(const uint32_t* planes, int64_t n,
+                               int64_t n_cases, const uint64_t* live,
+                               int32_t* out_counts);
+int gpe_host_hit_weighted_sums(const uint32_t* planes, int64_t n,
+                               int64_t n_cases, const double* weights, int G,
+                               double* out, double* out_lo);
+int gpe_host_hit_shared_sums(const uint32_t* planes, int64_t n,
+                             int64_t n_cases, const uint64_t* live,
+                             int32_t* out_counts, double* out, double* out_lo);
+
 /* Device tournament selection that replays the reference's random stream:
  * selTournament (deap/tools/selection.py:51-69, aspirants drawn by selRandom
  * :15-28, i.e. random.choice) — k tournaments of tournsize aspirants, the
