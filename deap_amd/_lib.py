@@ -1122,20 +1122,13 @@ class Context(object):
         advances its state.  Returns (indices, failed) as :meth:`lexicase`."""
         version, words, gauss = rng.getstate()
         st = np.asarray(words, dtype=np.uint32)
-        if planes is None:
-            n, n_cases, ptr = 0, 0, None
-        else:
-            units = (int(n_cases) + 31) // 32
-            planes = np.ascontiguousarray(planes, dtype=np.uint32)
-            if planes.shape != (int(n), units):
-                raise ValueError("lexicase_bits: planes must be uint32 "
-                                 "[%d, %d]" % (n, units))
-            ptr = _ptr(planes)
+        rows, n, n_cases, cases, ptr, keep = self._planes_arg(
+            "lexicase_bits", planes, n, n_cases)
         out = np.zeros(max(int(k), 1), dtype=np.int32)
         failed = ctypes.c_int64(-1)
-        self._check(self.lib.gpe_lexicase_bits(self.h, ptr, int(n),
-                                               int(n_cases), _ptr(st), int(k),
-                                               _ptr(out), ctypes.byref(failed)),
+        self._check(self.lib.gpe_lexicase_bits(self.h, ptr, n, n_cases,
+                                               _ptr(st), int(k), _ptr(out),
+                                               ctypes.byref(failed)),
                     "gpe_lexicase_bits")
         rng.setstate((version, tuple(int(w) for w in st), gauss))
         done = int(k) if failed.value < 0 else failed.value
@@ -1170,19 +1163,12 @@ class Context(object):
         """gpe_lexicase_bits_par: :meth:`lexicase_par`'s rule on 0/1 hits,
         every case maximised.  *planes* as :meth:`lexicase_bits` takes them
         (None: the last run_hit_planes' matrix on the device)."""
-        if planes is None:
-            n, n_cases, ptr = 0, 0, None
-        else:
-            units = (int(n_cases) + 31) // 32
-            planes = np.ascontiguousarray(planes, dtype=np.uint32)
-            if planes.shape != (int(n), units):
-                raise ValueError("lexicase_bits_par: planes must be uint32 "
-                                 "[%d, %d]" % (n, units))
-            ptr = _ptr(planes)
+        rows, n, n_cases, cases, ptr, keep = self._planes_arg(
+            "lexicase_bits_par", planes, n, n_cases)
         out = np.zeros(max(int(k), 1), dtype=np.int32)
         failed = ctypes.c_int64(-1)
         self._check(self.lib.gpe_lexicase_bits_par(
-            self.h, ptr, int(n), int(n_cases),
+            self.h, ptr, n, n_cases,
             int(seed) & 0xFFFFFFFFFFFFFFFF, int(k), _ptr(out),
             ctypes.byref(failed)), "gpe_lexicase_bits_par")
         return out[:int(k)], failed.value
@@ -1194,23 +1180,15 @@ class Context(object):
         takes them, or None for the resident matrix of the loaded programs
         (*n*, *n_cases* are then the context's).  The masks' pad bits are
         cleared by the library; nothing resident is disturbed."""
-        if planes is None:
-            masks = _check_group_masks("hit_group_counts", masks, self.n_cases)
-            rows, n, n_cases, ptr = self.n_prog, 0, 0, None
-        else:
-            masks = _check_group_masks("hit_group_counts", masks, n_cases)
-            planes = np.ascontiguousarray(planes, dtype=np.uint32)
-            if planes.shape != (int(n), masks.shape[1]):
-                raise ValueError("hit_group_counts: planes must be uint32 "
-                                 "[%d, %d]" % (n, masks.shape[1]))
-            rows, ptr = int(n), planes
+        # (the masks first: that order of errors is the call's)
+        masks = _check_group_masks("hit_group_counts", masks,
+                                   self.n_cases if planes is None else n_cases)
+        rows, n, n_cases, cases, ptr, keep = self._planes_arg(
+            "hit_group_counts", planes, n, n_cases)
         G = masks.shape[0]
         out = np.zeros((max(rows, 1), max(G, 1)), dtype=np.int32)
-        if ptr is not None:
-            # (a matrix of no rows is still the caller's, not the resident one)
-            ptr = _ptr(planes if planes.size else out)
         self._check(self.lib.gpe_hit_group_counts(
-            self.h, ptr, int(n), int(n_cases), _ptr(masks), G, _ptr(out)),
+            self.h, ptr, n, n_cases, _ptr(masks), G, _ptr(out)),
             "gpe_hit_group_counts")
         return out[:rows, :G].astype(np.int64)
 
@@ -1221,16 +1199,20 @@ class Context(object):
                     "gpe_last_hit_group_ms")
         return float(ms.value)
 
-    def _weights_matrix(self, what, planes, n, n_cases):
-        """The matrix argument of the case-weight calls →
+    def _planes_arg(self, what, planes, n, n_cases):
+        """The *planes* argument of every call on a hit matrix →
         ``(rows, n, n_cases, cases, ptr, keep)``: *rows* / *cases* the shape
-        the outputs need, *n* / *n_cases* / *ptr* the library's arguments."""
+        the outputs need, *n* / *n_cases* / *ptr* the library's arguments
+        (None: the resident matrix, whose sizes the library knows; *keep*
+        holds what *ptr* points into).  The sizes themselves are the
+        library's to refuse."""
         if planes is None:
             return self.n_prog, 0, 0, self.n_cases, None, None
-        planes = _check_planes(what, planes, n_cases)
-        if planes.shape[0] != int(n):
+        units = (int(n_cases) + 31) // 32
+        planes = np.ascontiguousarray(planes, dtype=np.uint32)
+        if planes.shape != (int(n), units):
             raise ValueError("%s: planes must be uint32 [%d, %d]"
-                             % (what, n, planes.shape[1]))
+                             % (what, n, units))
         # (a matrix of no rows is still the caller's, not the resident one)
         keep = planes if planes.size else np.zeros(1, dtype=np.uint32)
         return int(n), int(n), int(n_cases), int(n_cases), _ptr(keep), keep
@@ -1243,7 +1225,7 @@ class Context(object):
         thresholds the F machine's per-case matrix, as
         :meth:`informed_cases`).  *live*: uint64 [ceil(n / 64)]
         (:func:`pack_live_mask`) or None.  Nothing resident is disturbed."""
-        rows, n, n_cases, cases, ptr, keep = self._weights_matrix(
+        rows, n, n_cases, cases, ptr, keep = self._planes_arg(
             "case_solve_counts", planes, n, n_cases)
         live = _check_live("case_solve_counts", live, rows)
         out = np.zeros(max(cases, 1), dtype=np.int32)
@@ -1258,7 +1240,7 @@ class Context(object):
         ``[G, n_cases]`` (or 1-D), *G* in 1 .. 8, checked by
         :func:`check_case_weights`.  The matrix as
         :meth:`case_solve_counts`."""
-        rows, n, n_cases, cases, ptr, keep = self._weights_matrix(
+        rows, n, n_cases, cases, ptr, keep = self._planes_arg(
             "hit_weighted_sums", planes, n, n_cases)
         w = check_case_weights("hit_weighted_sums", weights, cases)
         G = w.shape[0]
@@ -1274,7 +1256,7 @@ class Context(object):
         program's sum of ``1 / counts[c]`` over the cases it hits (implicit
         fitness sharing), the weights made on the device.  The matrix and
         *live* as :meth:`case_solve_counts`."""
-        rows, n, n_cases, cases, ptr, keep = self._weights_matrix(
+        rows, n, n_cases, cases, ptr, keep = self._planes_arg(
             "hit_shared_sums", planes, n, n_cases)
         live = _check_live("hit_shared_sums", live, rows)
         cnt = np.zeros(max(cases, 1), dtype=np.int32)
@@ -1301,18 +1283,12 @@ class Context(object):
         context's): the last run_hit_planes' on the B machine, the last
         run_abserr_cases' thresholded at *eps* on the F machine.  *seed*: the
         64-bit seed of the tie-break keys.  Nothing resident is disturbed."""
-        if planes is None:
-            n, n_cases, ptr = 0, 0, None
-        else:
-            planes = _check_planes("informed_cases", planes, n_cases)
-            if planes.shape[0] != int(n):
-                raise ValueError("informed_cases: planes must be uint32 "
-                                 "[%d, %d]" % (n, planes.shape[1]))
-            ptr = _ptr(planes)
+        rows, n, n_cases, cases, ptr, keep = self._planes_arg(
+            "informed_cases", planes, n, n_cases)
         idx = np.zeros(max(int(m), 1), dtype=np.int64)
         dist = np.zeros(max(int(m), 1), dtype=np.int32)
         self._check(self.lib.gpe_informed_cases(
-            self.h, ptr, int(n), int(n_cases), float(eps),
+            self.h, ptr, n, n_cases, float(eps),
             int(seed) & 0xFFFFFFFFFFFFFFFF, int(m), _ptr(idx), _ptr(dist)),
             "gpe_informed_cases")
         return idx[:int(m)], dist[:int(m)]

@@ -271,15 +271,11 @@ int gpe_lexicase_bits(gpe_ctx* ctx, const uint32_t* planes, int64_t n, int64_t n
   if (mt_state[kMtN] > (uint32_t)kMtN)
     return fail(ctx, GPE_E_INVALID, "lexicase_bits: MT19937 position beyond 624");
   if (failed) *failed = -1;
-  if (!planes) {                   // the matrix of the last gpe_run_hit_planes
-    if (!ctx->hit_valid || ctx->n_prog <= 0 || ctx->hit_n != ctx->n_prog ||
-        ctx->hit_cases != ctx->n_cases)
-      return fail(ctx, GPE_E_STATE,
-                  "no hit planes of the loaded programs on the device (gpe_run_hit_planes "
-                  "first)");
-    n = ctx->hit_n;
-    n_cases = ctx->hit_cases;
-  }
+  HitMatrix hm;
+  if (int rc = hit_matrix_which(ctx, "lexicase_bits", planes, n, n_cases, false, 0.0, &hm))
+    return rc;
+  n = hm.n;
+  n_cases = hm.n_cases;
   if (n < 0 || n_cases <= 0 || n > INT32_MAX || n_cases >= (1ll << 31))
     return fail(ctx, GPE_E_INVALID, "lexicase_bits: bad or oversized input");
   if (n == 0) {                    // random.choice([]) at the first selection
@@ -287,27 +283,9 @@ int gpe_lexicase_bits(gpe_ctx* ctx, const uint32_t* planes, int64_t n, int64_t n
     return 0;
   }
   if (k == 0) return 0;
-  const int64_t units = (n_cases + 31) / 32;
-  const int64_t W = (n + 63) / 64;
-  const size_t qwords = (size_t)units * 32 * (size_t)W;
-  const unsigned long long* Q = nullptr;
-  if (planes) {
-    const size_t words = (size_t)n * (size_t)units;
-    if (ensure(ctx, &ctx->d_lexb_in, &ctx->lexb_in_cap, words) ||
-        ensure(ctx, &ctx->d_lexb_q, &ctx->lexb_q_cap, qwords))
-      return GPE_E_HIP;
-    const HostPiece pc[1] = {{ctx->d_lexb_in, planes, words * sizeof(uint32_t)}};
-    if (int rc = h2d_staged(ctx, pc, 1)) return rc;
-    if (int rc = launch_hit_transpose(ctx, ctx->d_lexb_in, n, units, ctx->d_lexb_q)) return rc;
-    Q = ctx->d_lexb_q;
-  } else {
-    if (!ctx->hit_t_valid) {
-      if (ensure(ctx, &ctx->d_hit_t, &ctx->hit_t_cap, qwords)) return GPE_E_HIP;
-      if (int rc = launch_hit_transpose(ctx, ctx->d_hit, n, units, ctx->d_hit_t)) return rc;
-      ctx->hit_t_valid = true;
-    }
-    Q = ctx->d_hit_t;
-  }
+  if (int rc = hit_matrix_device(ctx, &hm, true)) return rc;
+  const int64_t W = hm.W;
+  const unsigned long long* Q = hm.Q;
   // candidates and permutation: LDS while ceil(n / 32) + n_cases words fit
   // 48 KiB (gpe_lexicase's rule), else device scratch
   const size_t need = (size_t)(2 * W + n_cases) * sizeof(uint32_t);

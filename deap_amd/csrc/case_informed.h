@@ -1,5 +1,5 @@
 // Part of gpeval.hip's single translation unit (included there once, after
-// case_bits.h): informed down-sampling — a farthest-first subset of the cases
+// hit_matrix.h): informed down-sampling — a farthest-first subset of the cases
 // from the resident per-case matrix — gpe_informed_cases,
 // gpe_host_informed_cases, gpe_host_hit_threshold.
 //
@@ -8,7 +8,8 @@
 // case_bits.h already builds: Q = uint64[32 n_units][W], W = ceil(n / 64),
 // program i at bit i % 64 of word i / 64, pad programs 0.  A regression
 // matrix (d_case_out, double[n][n_cases] of absolute errors) is first turned
-// into program-major hit planes by hit_threshold and transposed like any other.
+// into program-major hit planes by hit_threshold and transposed like any other
+// (hit_matrix.h, which resolves the matrix of a call; kInfBlock is there too).
 //
 // The traversal: key[c] = the (c + 1)-th output of SplitMix64(seed) orders the
 // cases totally by (key, c).  The first pick is the smallest case in that
@@ -24,7 +25,6 @@
 #pragma once
 namespace {
 
-constexpr int kInfBlock = 256;              // 4 waves
 constexpr int64_t kInfMaxBlocks = 1024;     // partials a block reduces per launch
 constexpr size_t kInfPivotLds = 32 * 1024;  // the pivot row is staged in LDS up to here
 
@@ -47,38 +47,6 @@ __host__ __device__ inline bool informed_better(const InfCand& a, const InfCand&
   if (a.md < 0) return false;
   if (a.key != b.key) return a.key < b.key;
   return a.c < b.c;
-}
-
-// E double[n][C] (absolute errors) into hit planes H uint32[n][units]: bit
-// c % 32 of word c / 32 is e <= eps for a finite e (nan and inf never hit, also
-// with eps = inf), pad bits 0.  A wave takes one program and 32 stretches of 64
-// cases: a ballot per stretch gives two words, kept by lanes 2 s and 2 s + 1,
-// and the wave then stores its 64 words side by side.
-__global__ __launch_bounds__(kInfBlock) void hit_threshold(const double* __restrict__ E,
-                                                           int64_t n, int64_t C, int64_t units,
-                                                           double eps, uint32_t* __restrict__ H) {
-  const int lane = threadIdx.x & 63;
-  const int64_t chunks = (units + 63) / 64;
-  const int64_t total = n * chunks;
-  for (int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); item < total;
-       item += (int64_t)gridDim.x * 4) {
-    const int64_t p = item / chunks, ch = item - p * chunks;
-    const double* row = E + p * C;
-    const int64_t c0 = ch * 2048;
-    unsigned long long mine = 0;
-    for (int s = 0; s < 32 && c0 + (int64_t)s * 64 < C; ++s) {
-      const int64_t c = c0 + (int64_t)s * 64 + lane;
-      bool h = false;
-      if (c < C) {
-        const double e = row[c];
-        h = e <= eps && e - e == 0.0;               // (inf - inf and nan - nan are nan)
-      }
-      const unsigned long long m = __builtin_amdgcn_ballot_w64(h);
-      if ((lane >> 1) == s) mine = m;
-    }
-    const int64_t w = ch * 64 + lane;
-    if (w < units) H[p * units + w] = (uint32_t)(mine >> (32 * (lane & 1)));
-  }
 }
 
 // the best of the block's candidates in every thread (all kInfBlock threads
@@ -307,66 +275,12 @@ int gpe_informed_cases(gpe_ctx* ctx, const uint32_t* planes, int64_t n, int64_t 
                        int32_t* out_dist) {
   if (!ctx || !out_idx || !out_dist) return GPE_E_INVALID;
   HIPCHK(hipSetDevice(ctx->device));
-  // (the F machine after a typed hit-planes run: its planes, as on the B
-  // machine; a later per-case run clears hit_valid and decides again)
-  const bool f_route = !planes && ctx->machine == GPE_MACHINE_F && !ctx->hit_valid;
-  if (!planes) {
-    if (f_route) {                 // the matrix of the last per-case run, thresholded
-      if (!ctx->d_case_out || ctx->n_prog <= 0 || ctx->case_stale)
-        return fail(ctx, GPE_E_STATE, "no per-case values on the device");
-      if (ctx->case_n != ctx->n_prog)       // (the matrix has case_n rows)
-        return fail(ctx, GPE_E_STATE,
-                    "no per-case values of the loaded programs on the device (another "
-                    "batch was loaded since the per-case run)");
-      if (!(eps >= 0.0))
-        return fail(ctx, GPE_E_ARG, "informed_cases: eps must be >= 0 (and not nan)");
-      n = ctx->n_prog;
-      n_cases = ctx->n_cases;
-    } else {                       // the matrix of the last gpe_run_hit_planes
-      if (!ctx->hit_valid || ctx->n_prog <= 0 || ctx->hit_n != ctx->n_prog ||
-          ctx->hit_cases != ctx->n_cases)
-        return fail(ctx, GPE_E_STATE,
-                    "no hit planes of the loaded programs on the device (gpe_run_hit_planes "
-                    "first)");
-      n = ctx->hit_n;
-      n_cases = ctx->hit_cases;
-    }
-  }
-  if (int rc = informed_check_m(ctx, n, n_cases, m)) return rc;
-  const int64_t units = (n_cases + 31) / 32;
-  const int64_t W = (n + 63) / 64;
-  const size_t words = (size_t)n * (size_t)units;
-  const size_t qwords = (size_t)units * 32 * (size_t)W;
-  const unsigned long long* Q = nullptr;
-  if (planes) {
-    if (ensure(ctx, &ctx->d_lexb_in, &ctx->lexb_in_cap, words) ||
-        ensure(ctx, &ctx->d_lexb_q, &ctx->lexb_q_cap, qwords))
-      return GPE_E_HIP;
-    const HostPiece pc[1] = {{ctx->d_lexb_in, planes, words * sizeof(uint32_t)}};
-    if (int rc = h2d_staged(ctx, pc, 1)) return rc;
-    if (int rc = launch_hit_transpose(ctx, ctx->d_lexb_in, n, units, ctx->d_lexb_q)) return rc;
-    Q = ctx->d_lexb_q;
-  } else if (f_route) {
-    // planes and transpose of their own: d_case_out, d_hit and hit_valid stay
-    if (ensure(ctx, &ctx->d_inf_hit, &ctx->inf_hit_cap, words) ||
-        ensure(ctx, &ctx->d_inf_q, &ctx->inf_q_cap, qwords))
-      return GPE_E_HIP;
-    const int64_t items = n * ((units + 63) / 64);
-    const unsigned gx = (unsigned)std::min<int64_t>((items + 3) / 4, 65536);
-    hipLaunchKernelGGL(hit_threshold, dim3(gx), dim3(kInfBlock), 0, ctx->stream,
-                       ctx->d_case_out, n, n_cases, units, eps, ctx->d_inf_hit);
-    HIPCHK(hipGetLastError());
-    if (int rc = launch_hit_transpose(ctx, ctx->d_inf_hit, n, units, ctx->d_inf_q)) return rc;
-    Q = ctx->d_inf_q;
-  } else {
-    if (!ctx->hit_t_valid) {
-      if (ensure(ctx, &ctx->d_hit_t, &ctx->hit_t_cap, qwords)) return GPE_E_HIP;
-      if (int rc = launch_hit_transpose(ctx, ctx->d_hit, n, units, ctx->d_hit_t)) return rc;
-      ctx->hit_t_valid = true;
-    }
-    Q = ctx->d_hit_t;
-  }
-  if (int rc = launch_informed(ctx, Q, n, n_cases, seed, m)) return rc;
+  HitMatrix hm;
+  if (int rc = hit_matrix_which(ctx, "informed_cases", planes, n, n_cases, true, eps, &hm))
+    return rc;
+  if (int rc = informed_check_m(ctx, hm.n, hm.n_cases, m)) return rc;
+  if (int rc = hit_matrix_device(ctx, &hm, true)) return rc;
+  if (int rc = launch_informed(ctx, hm.Q, hm.n, hm.n_cases, seed, m)) return rc;
   if (int rc = values_to_host(ctx, out_idx, ctx->d_inf_idx, (size_t)m * sizeof(int64_t)))
     return rc;
   return values_to_host(ctx, out_dist, ctx->d_inf_dist, (size_t)m * sizeof(int32_t));

@@ -501,10 +501,13 @@ struct gpe_ctx {
   // plane into d_hit, uint32[hit_n][hit_units].  hit_valid: d_hit holds the
   // matrix of the active case set (gpe_select_cases and gpe_set_cases clear
   // it).  d_hit_t: the same bits case-major, uint64[32 hit_units][hit_w64]
-  // (program i at bit i % 64 of word i / 64), built by hit_transpose at the
-  // first gpe_lexicase_bits(NULL) after the run (hit_t_valid).  d_lexb_in /
-  // d_lexb_q: a caller's host matrix and its transpose; d_lexb_scratch: the
-  // candidate words and the permutation where they do not fit LDS.
+  // (program i at bit i % 64 of word i / 64), built by hit_transpose for the
+  // first call after the run that reads the resident matrix case-major
+  // (hit_t_valid).  d_lexb_in / d_lexb_q: a caller's host matrix and its
+  // transpose.  Which of the two a call means, and who fills them, is
+  // hit_matrix.h's alone (its head describes the routes).  d_lexb_scratch:
+  // gpe_lexicase_bits' candidate words and permutation where they do not fit
+  // LDS.
   // On the F machine the matrix is a typed hit-planes run's
   // (gpe_run_typed_hit_planes, typed_hits.h): hits_on then makes the
   // HITS_BOOL routes store the matches they count; a per-case run
@@ -525,10 +528,10 @@ struct gpe_ctx {
   size_t lexb_q_cap = 0;
   uint32_t* d_lexb_scratch = nullptr;
   size_t lexb_scratch_cap = 0;
-  // Informed down-sampling (gpe_informed_cases, case_informed.h).  d_inf_hit /
-  // d_inf_q: the F machine's per-case matrix thresholded into hit planes
-  // uint32[n][n_units] and their case-major transpose — scratch of the call,
-  // never d_hit / d_hit_t (hit_valid is the B machine's).  d_inf_mind: each
+  // d_inf_hit / d_inf_q: the F machine's per-case matrix thresholded into hit
+  // planes uint32[n][n_units] and their case-major transpose — hit_matrix.h's
+  // third route, scratch of the call, never d_hit / d_hit_t.
+  // Informed down-sampling (gpe_informed_cases, case_informed.h).  d_inf_mind: each
   // case's distance to its nearest chosen case (-1: chosen); d_inf_part: two
   // sets of block partials (key, mind << 32 | case), written by one launch and
   // reduced by the next; d_inf_idx / d_inf_dist: the picks.
@@ -579,7 +582,7 @@ struct gpe_ctx {
   size_t lexp_vals_cap = 0;
   // Masked counts of the hit planes (gpe_hit_group_counts, hit_groups.h): a
   // call's masks uint32[G][n_units], pad bits cleared, and its counts
-  // int32[n][G].  A caller's host matrix goes through d_lexb_in.
+  // int32[n][G].  The matrix is hit_matrix.h's.
   uint32_t* d_hitgrp_masks = nullptr;
   size_t hitgrp_masks_cap = 0;
   int32_t* d_hitgrp_out = nullptr;

@@ -2882,6 +2882,7 @@ int gpe_run_values_bits(gpe_ctx* ctx, uint32_t* out_planes) {
   return values_to_host(ctx, out_planes, ctx->d_vals, words * sizeof(uint32_t));
 }
 
+#include "hit_matrix.h"
 #include "case_bits.h"
 #include "case_informed.h"
 #include "lexicase_par.h"

@@ -141,6 +141,20 @@ void hitgrp_launch(gpe_ctx* ctx, const uint32_t* planes, int64_t n, int64_t unit
   }
 }
 
+void hitgrp_launch_g(gpe_ctx* ctx, int G, const uint32_t* planes, int64_t n, int64_t units,
+                     const uint32_t* masks, int32_t* out) {
+  switch (G) {
+    case 1: hitgrp_launch<1>(ctx, planes, n, units, masks, out); break;
+    case 2: hitgrp_launch<2>(ctx, planes, n, units, masks, out); break;
+    case 3: hitgrp_launch<3>(ctx, planes, n, units, masks, out); break;
+    case 4: hitgrp_launch<4>(ctx, planes, n, units, masks, out); break;
+    case 5: hitgrp_launch<5>(ctx, planes, n, units, masks, out); break;
+    case 6: hitgrp_launch<6>(ctx, planes, n, units, masks, out); break;
+    case 7: hitgrp_launch<7>(ctx, planes, n, units, masks, out); break;
+    default: hitgrp_launch<8>(ctx, planes, n, units, masks, out); break;
+  }
+}
+
 // the masks with their pad bits cleared, uint32[G][units]
 std::vector<uint32_t> hitgrp_clean_masks(const uint32_t* masks, int G, int64_t n_cases) {
   const int64_t units = (n_cases + 31) / 32;
@@ -182,15 +196,11 @@ int gpe_hit_group_counts(gpe_ctx* ctx, const uint32_t* planes, int64_t n, int64_
   }
   if (!masks) return fail(ctx, GPE_E_ARG, "hit_group_counts: masks is NULL");
   HIPCHK(hipSetDevice(ctx->device));
-  if (!planes) {                   // the matrix of the last hit-planes run
-    if (!ctx->hit_valid || ctx->n_prog <= 0 || ctx->hit_n != ctx->n_prog ||
-        ctx->hit_cases != ctx->n_cases)
-      return fail(ctx, GPE_E_STATE,
-                  "no hit planes of the loaded programs on the device (gpe_run_hit_planes "
-                  "first)");
-    n = ctx->hit_n;
-    n_cases = ctx->hit_cases;
-  }
+  HitMatrix hm;
+  if (int rc = hit_matrix_which(ctx, "hit_group_counts", planes, n, n_cases, false, 0.0, &hm))
+    return rc;
+  n = hm.n;
+  n_cases = hm.n_cases;
   if (n < 0) {
     snprintf(buf, sizeof(buf), "hit_group_counts: n = %lld individuals (need >= 0)",
              (long long)n);
@@ -203,36 +213,16 @@ int gpe_hit_group_counts(gpe_ctx* ctx, const uint32_t* planes, int64_t n, int64_
   }
   if (n == 0) return 0;
   if (!out) return fail(ctx, GPE_E_ARG, "hit_group_counts: out is NULL");
-  const int64_t units = (n_cases + 31) / 32;
   const std::vector<uint32_t> m = hitgrp_clean_masks(masks, G, n_cases);
-  const uint32_t* d_planes = ctx->d_hit;
   if (ensure(ctx, &ctx->d_hitgrp_masks, &ctx->hitgrp_masks_cap, m.size()) ||
       ensure(ctx, &ctx->d_hitgrp_out, &ctx->hitgrp_out_cap, (size_t)n * (size_t)G))
     return GPE_E_HIP;
-  if (planes) {
-    // (a caller's matrix goes where gpe_lexicase_bits puts one: scratch)
-    const size_t words = (size_t)n * (size_t)units;
-    if (ensure(ctx, &ctx->d_lexb_in, &ctx->lexb_in_cap, words)) return GPE_E_HIP;
-    const HostPiece pc[2] = {{ctx->d_lexb_in, planes, words * sizeof(uint32_t)},
-                             {ctx->d_hitgrp_masks, m.data(), m.size() * sizeof(uint32_t)}};
-    if (int rc = h2d_staged(ctx, pc, 2)) return rc;
-    d_planes = ctx->d_lexb_in;
-  } else {
-    const HostPiece pc[1] = {{ctx->d_hitgrp_masks, m.data(), m.size() * sizeof(uint32_t)}};
-    if (int rc = h2d_staged(ctx, pc, 1)) return rc;
-  }
+  // (the masks travel with a caller's matrix; the counts read H alone)
+  const HostPiece pc[1] = {{ctx->d_hitgrp_masks, m.data(), m.size() * sizeof(uint32_t)}};
+  if (int rc = hit_matrix_device(ctx, &hm, false, pc, 1)) return rc;
   // (ev_redo: the context's timed pair; no run is in flight in this call)
   HIPCHK(hipEventRecord(ctx->ev_redo[0], ctx->stream));
-  switch (G) {
-    case 1: hitgrp_launch<1>(ctx, d_planes, n, units, ctx->d_hitgrp_masks, ctx->d_hitgrp_out); break;
-    case 2: hitgrp_launch<2>(ctx, d_planes, n, units, ctx->d_hitgrp_masks, ctx->d_hitgrp_out); break;
-    case 3: hitgrp_launch<3>(ctx, d_planes, n, units, ctx->d_hitgrp_masks, ctx->d_hitgrp_out); break;
-    case 4: hitgrp_launch<4>(ctx, d_planes, n, units, ctx->d_hitgrp_masks, ctx->d_hitgrp_out); break;
-    case 5: hitgrp_launch<5>(ctx, d_planes, n, units, ctx->d_hitgrp_masks, ctx->d_hitgrp_out); break;
-    case 6: hitgrp_launch<6>(ctx, d_planes, n, units, ctx->d_hitgrp_masks, ctx->d_hitgrp_out); break;
-    case 7: hitgrp_launch<7>(ctx, d_planes, n, units, ctx->d_hitgrp_masks, ctx->d_hitgrp_out); break;
-    default: hitgrp_launch<8>(ctx, d_planes, n, units, ctx->d_hitgrp_masks, ctx->d_hitgrp_out); break;
-  }
+  hitgrp_launch_g(ctx, G, hm.H, n, hm.units, ctx->d_hitgrp_masks, ctx->d_hitgrp_out);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(ctx->ev_redo[1], ctx->stream));
   if (int rc = values_to_host(ctx, out, ctx->d_hitgrp_out, (size_t)n * (size_t)G * sizeof(int32_t)))

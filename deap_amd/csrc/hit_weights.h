@@ -238,124 +238,41 @@ bool hw_weights_ok(const double* w, size_t count) {
   return true;
 }
 
-// The matrix of a call, by gpe_informed_cases' three routes: a caller's planes
-// (uploaded to d_lexb_in / d_lexb_q), the F machine's d_case_out thresholded
-// into d_inf_hit / d_inf_q, or the resident d_hit / d_hit_t.  H is always
-// made, Q when want_q.  The call's other host inputs travel with the planes in
-// one staged copy (the staging buffer is not reused before the stream has read
-// it): weights double[G][n_cases] into d_hw_w, the live mask into d_hw_live
-// (d_live; nullptr: all live).  n == 0 on return: nothing to do.
-struct HwMatrix {
-  const uint32_t* H = nullptr;
-  const unsigned long long* Q = nullptr;
-  const unsigned long long* d_live = nullptr;
-  int64_t n = 0, n_cases = 0, units = 0;
-};
-
-int hw_matrix(gpe_ctx* ctx, const char* what, const uint32_t* planes, int64_t n, int64_t n_cases,
-              double eps, bool want_q, const double* weights, int G, const uint64_t* live,
-              HwMatrix* m) {
+// The sizes of a case-weight call, after hit_matrix_which (hit_matrix.h) has
+// filled them in.  want_q: the call counts on the case-major planes, whose
+// programs an int32 indexes.
+int hw_check(gpe_ctx* ctx, const char* what, const HitMatrix& m, bool want_q) {
   char buf[160];
-  const bool f_route = !planes && ctx->machine == GPE_MACHINE_F && !ctx->hit_valid;
-  if (!planes) {
-    if (f_route) {                 // the matrix of the last per-case run, thresholded
-      if (!ctx->d_case_out || ctx->n_prog <= 0 || ctx->case_stale)
-        return fail(ctx, GPE_E_STATE, "no per-case values on the device");
-      if (ctx->case_n != ctx->n_prog)
-        return fail(ctx, GPE_E_STATE,
-                    "no per-case values of the loaded programs on the device (another "
-                    "batch was loaded since the per-case run)");
-      if (!(eps >= 0.0)) {
-        snprintf(buf, sizeof(buf), "%s: eps must be >= 0 (and not nan)", what);
-        return fail(ctx, GPE_E_ARG, buf);
-      }
-      n = ctx->n_prog;
-      n_cases = ctx->n_cases;
-    } else {                       // the matrix of the last hit-planes run
-      if (!ctx->hit_valid || ctx->n_prog <= 0 || ctx->hit_n != ctx->n_prog ||
-          ctx->hit_cases != ctx->n_cases)
-        return fail(ctx, GPE_E_STATE,
-                    "no hit planes of the loaded programs on the device (gpe_run_hit_planes "
-                    "first)");
-      n = ctx->hit_n;
-      n_cases = ctx->hit_cases;
-    }
-  }
-  if (n < 0) {
-    snprintf(buf, sizeof(buf), "%s: n = %lld individuals (need >= 0)", what, (long long)n);
+  if (m.n < 0) {
+    snprintf(buf, sizeof(buf), "%s: n = %lld individuals (need >= 0)", what, (long long)m.n);
     return fail(ctx, GPE_E_ARG, buf);
   }
-  if (n_cases < 1 || n_cases >= (1ll << 31)) {
+  if (m.n_cases < 1 || m.n_cases >= (1ll << 31)) {
     snprintf(buf, sizeof(buf), "%s: n_cases = %lld (need 1 .. 2^31 - 1)", what,
-             (long long)n_cases);
+             (long long)m.n_cases);
     return fail(ctx, GPE_E_ARG, buf);
   }
-  if (want_q && n > INT32_MAX) {
+  if (want_q && m.n > INT32_MAX) {
     snprintf(buf, sizeof(buf), "%s: n = %lld individuals (the counts need n <= 2^31 - 1)", what,
-             (long long)n);
+             (long long)m.n);
     return fail(ctx, GPE_E_ARG, buf);
-  }
-  m->n = n;
-  m->n_cases = n_cases;
-  m->units = (n_cases + 31) / 32;
-  if (n == 0) return 0;
-  const int64_t units = m->units, W = (n + 63) / 64;
-  const size_t words = (size_t)n * (size_t)units;
-  const size_t qwords = (size_t)units * 32 * (size_t)W;
-  HostPiece pc[3];
-  int n_pc = 0;
-  if (weights) {
-    const size_t wn = (size_t)G * (size_t)n_cases;
-    if (!hw_weights_ok(weights, wn)) {
-      snprintf(buf, sizeof(buf), "%s: every weight must be finite and >= 0", what);
-      return fail(ctx, GPE_E_ARG, buf);
-    }
-    if (ensure(ctx, &ctx->d_hw_w, &ctx->hw_w_cap, wn)) return GPE_E_HIP;
-    pc[n_pc++] = {ctx->d_hw_w, weights, wn * sizeof(double)};
-  }
-  if (live) {
-    if (ensure(ctx, &ctx->d_hw_live, &ctx->hw_live_cap, (size_t)W)) return GPE_E_HIP;
-    pc[n_pc++] = {ctx->d_hw_live, live, (size_t)W * sizeof(uint64_t)};
-    m->d_live = ctx->d_hw_live;
-  }
-  if (planes) {
-    if (ensure(ctx, &ctx->d_lexb_in, &ctx->lexb_in_cap, words)) return GPE_E_HIP;
-    pc[n_pc++] = {ctx->d_lexb_in, planes, words * sizeof(uint32_t)};
-  }
-  if (int rc = h2d_staged(ctx, pc, n_pc)) return rc;
-  if (planes) {
-    m->H = ctx->d_lexb_in;
-    if (want_q) {
-      if (ensure(ctx, &ctx->d_lexb_q, &ctx->lexb_q_cap, qwords)) return GPE_E_HIP;
-      if (int rc = launch_hit_transpose(ctx, ctx->d_lexb_in, n, units, ctx->d_lexb_q)) return rc;
-      m->Q = ctx->d_lexb_q;
-    }
-  } else if (f_route) {
-    // planes and transpose of their own: d_case_out, d_hit and hit_valid stay
-    if (ensure(ctx, &ctx->d_inf_hit, &ctx->inf_hit_cap, words)) return GPE_E_HIP;
-    const int64_t items = n * ((units + 63) / 64);
-    const unsigned gx = (unsigned)std::min<int64_t>((items + 3) / 4, 65536);
-    hipLaunchKernelGGL(hit_threshold, dim3(gx), dim3(kInfBlock), 0, ctx->stream,
-                       ctx->d_case_out, n, n_cases, units, eps, ctx->d_inf_hit);
-    HIPCHK(hipGetLastError());
-    m->H = ctx->d_inf_hit;
-    if (want_q) {
-      if (ensure(ctx, &ctx->d_inf_q, &ctx->inf_q_cap, qwords)) return GPE_E_HIP;
-      if (int rc = launch_hit_transpose(ctx, ctx->d_inf_hit, n, units, ctx->d_inf_q)) return rc;
-      m->Q = ctx->d_inf_q;
-    }
-  } else {
-    m->H = ctx->d_hit;
-    if (want_q) {
-      if (!ctx->hit_t_valid) {
-        if (ensure(ctx, &ctx->d_hit_t, &ctx->hit_t_cap, qwords)) return GPE_E_HIP;
-        if (int rc = launch_hit_transpose(ctx, ctx->d_hit, n, units, ctx->d_hit_t)) return rc;
-        ctx->hit_t_valid = true;
-      }
-      m->Q = ctx->d_hit_t;
-    }
   }
   return 0;
+}
+
+// The matrix of a counting call on the device, H and Q, its live mask
+// uint64[ceil(n / 64)] travelling with the planes into d_hw_live (*d_live;
+// nullptr: all live).
+int hw_matrix_live(gpe_ctx* ctx, HitMatrix* m, const uint64_t* live,
+                   const unsigned long long** d_live) {
+  HostPiece pc[1];
+  const size_t W = (size_t)((m->n + 63) / 64);
+  if (live) {
+    if (ensure(ctx, &ctx->d_hw_live, &ctx->hw_live_cap, W)) return GPE_E_HIP;
+    pc[0] = {ctx->d_hw_live, live, W * sizeof(uint64_t)};
+  }
+  *d_live = live ? ctx->d_hw_live : nullptr;
+  return hit_matrix_device(ctx, m, true, pc, live ? 1 : 0);
 }
 
 }  // namespace
@@ -413,18 +330,20 @@ int gpe_case_solve_counts(gpe_ctx* ctx, const uint32_t* planes, int64_t n, int64
   if (!ctx) return GPE_E_INVALID;
   if (!out_counts) return fail(ctx, GPE_E_ARG, "case_solve_counts: out_counts is NULL");
   HIPCHK(hipSetDevice(ctx->device));
-  HwMatrix m;
-  if (int rc = hw_matrix(ctx, "case_solve_counts", planes, n, n_cases, eps, true, nullptr, 0, live,
-                         &m))
+  HitMatrix m;
+  if (int rc = hit_matrix_which(ctx, "case_solve_counts", planes, n, n_cases, true, eps, &m))
     return rc;
+  if (int rc = hw_check(ctx, "case_solve_counts", m, true)) return rc;
   if (m.n == 0) {                  // nobody solves anything
     if (planes) std::fill(out_counts, out_counts + m.n_cases, 0);
     return 0;
   }
+  const unsigned long long* d_live = nullptr;
+  if (int rc = hw_matrix_live(ctx, &m, live, &d_live)) return rc;
   if (ensure(ctx, &ctx->d_hw_cnt, &ctx->hw_cnt_cap, (size_t)m.n_cases)) return GPE_E_HIP;
   // (ev_redo: the context's timed pair; no run is in flight in this call)
   HIPCHK(hipEventRecord(ctx->ev_redo[0], ctx->stream));
-  if (int rc = hw_launch_counts(ctx, m.Q, m.n, m.n_cases, m.d_live, ctx->d_hw_cnt, nullptr))
+  if (int rc = hw_launch_counts(ctx, m.Q, m.n, m.n_cases, d_live, ctx->d_hw_cnt, nullptr))
     return rc;
   HIPCHK(hipEventRecord(ctx->ev_redo[1], ctx->stream));
   if (int rc = values_to_host(ctx, out_counts, ctx->d_hw_cnt, (size_t)m.n_cases * sizeof(int32_t)))
@@ -447,12 +366,20 @@ int gpe_hit_weighted_sums(gpe_ctx* ctx, const uint32_t* planes, int64_t n, int64
   // (a NULL out is refused before anything is copied: n is known by now
   // unless the matrix is the resident one, which has programs)
   if (!out && (!planes || n > 0)) return fail(ctx, GPE_E_ARG, "hit_weighted_sums: out is NULL");
-  HwMatrix m;
-  if (int rc = hw_matrix(ctx, "hit_weighted_sums", planes, n, n_cases, eps, false, weights, G,
-                         nullptr, &m))
+  HitMatrix m;
+  if (int rc = hit_matrix_which(ctx, "hit_weighted_sums", planes, n, n_cases, true, eps, &m))
     return rc;
+  if (int rc = hw_check(ctx, "hit_weighted_sums", m, false)) return rc;
   if (m.n == 0) return 0;
-  if (ensure(ctx, &ctx->d_hw_out, &ctx->hw_out_cap, (size_t)m.n * (size_t)G)) return GPE_E_HIP;
+  const size_t wn = (size_t)G * (size_t)m.n_cases;
+  if (!hw_weights_ok(weights, wn))
+    return fail(ctx, GPE_E_ARG, "hit_weighted_sums: every weight must be finite and >= 0");
+  if (ensure(ctx, &ctx->d_hw_w, &ctx->hw_w_cap, wn) ||
+      ensure(ctx, &ctx->d_hw_out, &ctx->hw_out_cap, (size_t)m.n * (size_t)G))
+    return GPE_E_HIP;
+  // (the weights travel with a caller's matrix; the sums read H alone)
+  const HostPiece pc[1] = {{ctx->d_hw_w, weights, wn * sizeof(double)}};
+  if (int rc = hit_matrix_device(ctx, &m, false, pc, 1)) return rc;
   HIPCHK(hipEventRecord(ctx->ev_redo[0], ctx->stream));
   hw_launch_g(ctx, G, m.H, m.n, m.units, m.n_cases, ctx->d_hw_w, ctx->d_hw_out);
   HIPCHK(hipGetLastError());
@@ -468,14 +395,16 @@ int gpe_hit_shared_sums(gpe_ctx* ctx, const uint32_t* planes, int64_t n, int64_t
   if (!ctx) return GPE_E_INVALID;
   HIPCHK(hipSetDevice(ctx->device));
   if (!out && (!planes || n > 0)) return fail(ctx, GPE_E_ARG, "hit_shared_sums: out is NULL");
-  HwMatrix m;
-  if (int rc = hw_matrix(ctx, "hit_shared_sums", planes, n, n_cases, eps, true, nullptr, 0, live,
-                         &m))
+  HitMatrix m;
+  if (int rc = hit_matrix_which(ctx, "hit_shared_sums", planes, n, n_cases, true, eps, &m))
     return rc;
+  if (int rc = hw_check(ctx, "hit_shared_sums", m, true)) return rc;
   if (m.n == 0) {
     if (planes && out_counts) std::fill(out_counts, out_counts + m.n_cases, 0);
     return 0;
   }
+  const unsigned long long* d_live = nullptr;
+  if (int rc = hw_matrix_live(ctx, &m, live, &d_live)) return rc;
   if (ensure(ctx, &ctx->d_hw_cnt, &ctx->hw_cnt_cap, (size_t)m.n_cases) ||
       ensure(ctx, &ctx->d_hw_w, &ctx->hw_w_cap, (size_t)m.n_cases) ||
       ensure(ctx, &ctx->d_hw_out, &ctx->hw_out_cap, (size_t)m.n))
@@ -483,7 +412,7 @@ int gpe_hit_shared_sums(gpe_ctx* ctx, const uint32_t* planes, int64_t n, int64_t
   // counts, weights and sums follow each other on the stream: neither the
   // counts nor the weights visit the host in between
   HIPCHK(hipEventRecord(ctx->ev_redo[0], ctx->stream));
-  if (int rc = hw_launch_counts(ctx, m.Q, m.n, m.n_cases, m.d_live, ctx->d_hw_cnt, ctx->d_hw_w))
+  if (int rc = hw_launch_counts(ctx, m.Q, m.n, m.n_cases, d_live, ctx->d_hw_cnt, ctx->d_hw_w))
     return rc;
   hw_launch_g(ctx, 1, m.H, m.n, m.units, m.n_cases, ctx->d_hw_w, ctx->d_hw_out);
   HIPCHK(hipGetLastError());

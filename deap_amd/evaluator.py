@@ -1116,46 +1116,33 @@ class GPUEvaluator(object):
         the full case set (or :class:`SymbRegCaseErrors`' squared errors), *m*
         outside ``[1, full_n_cases]``.  If an individual of the batch raised,
         its exception is raised here, the first in order."""
-        name = type(self.spec).__name__
+        def own():
+            if not 1 <= m <= self.full_n_cases:
+                raise ValueError("informed_subsample: m must be in [1, %d] "
+                                 "(got %r)" % (self.full_n_cases, m))
         bits = getattr(self.spec, "hit_planes", False)
-        if self._lex_batch is None or self.case_subset is not None or \
-                not (bits or getattr(self.spec, "abs_cases", False)):
-            raise ValueError(
-                "informed_subsample: it needs the per-case matrix of a "
-                "BooleanCaseHits or SymbRegCaseAbsErrors evaluation on the "
-                "full case set (the spec is %s, %s, %s): subsample(None) and "
-                "evaluate the parent sample first"
-                % (name, "no per-case matrix is on the GPU"
-                   if self._lex_batch is None else "a per-case matrix is on "
-                   "the GPU", "no case subset is active"
-                   if self.case_subset is None else "a case subset is active"))
-        if bits and eps is not None:
-            raise ValueError("informed_subsample: eps applies to "
-                             "SymbRegCaseAbsErrors; BooleanCaseHits' cases "
-                             "are hits already (got eps=%r)" % (eps,))
-        if not 1 <= m <= self.full_n_cases:
-            raise ValueError("informed_subsample: m must be in [1, %d] (got "
-                             "%r)" % (self.full_n_cases, m))
-        last, results = self._lex_batch
-        if self.ctx.n_prog != len(last):
-            raise ValueError(
-                "informed_subsample: the context now holds %d programs, not "
-                "the %d of the last evaluate / map; evaluate the batch again"
-                % (self.ctx.n_prog, len(last)))
+        last, results = self._last_batch(
+            "informed_subsample", self.case_subset is None and
+            (bits or getattr(self.spec, "abs_cases", False)),
+            "it needs the per-case matrix of a BooleanCaseHits or "
+            "SymbRegCaseAbsErrors evaluation on the full case set (the spec "
+            "is %%s, %s, %s): subsample(None) and evaluate the parent sample "
+            "first" % ("no per-case matrix is on the GPU"
+                       if self._lex_batch is None else "a per-case matrix is "
+                       "on the GPU", "no case subset is active"
+                       if self.case_subset is None else "a case subset is "
+                       "active"),
+            eps=eps, hits_eps="BooleanCaseHits' cases are hits already",
+            own=own)
         for res in results:
             if isinstance(res, BaseException):
                 raise res
         if not last:
             raise ValueError("informed_subsample: the last evaluate / map "
                              "held no individuals")
-        if not bits:
-            eps = self.spec.hit_eps if eps is None else float(eps)
-            if not eps >= 0.0:
-                raise ValueError("informed_subsample: eps must be >= 0 (got "
-                                 "%r)" % (eps,))
+        eps = self._hit_eps("informed_subsample", eps)
         seed = random.getrandbits(64)
-        idx, dist = self.ctx.informed_cases(None, 0, 0, 0.0 if bits else eps,
-                                            seed, int(m))
+        idx, dist = self.ctx.informed_cases(None, 0, 0, eps, seed, int(m))
         self.last_informed_distances = dist
         if apply:
             self.subsample(idx)
@@ -1559,25 +1546,20 @@ class GPUEvaluator(object):
                                       "from 1 on every candidate survives "
                                       "every case and the selection is "
                                       "random.choice(individuals)"))
-        if self._lex_batch is None:
-            raise ValueError(
-                "select_lexicase: this evaluator's last evaluate / map left "
-                "no per-case matrix on the GPU (its spec is %s; evaluate "
-                "with SymbRegCaseAbsErrors, SymbRegCaseErrors or "
-                "BooleanCaseHits first)"
-                % type(self.spec).__name__)
-        last, results = self._lex_batch
-        if len(individuals) != len(last) or \
-                any(a is not b for a, b in zip(individuals, last)):
-            raise ValueError(
-                "select_lexicase: individuals must be the batch of this "
-                "evaluator's last evaluate / map, the same objects in the "
-                "same order: the GPU holds that batch's per-case errors")
-        if self.ctx.n_prog != len(last):
-            raise ValueError(
-                "select_lexicase: the context now holds %d programs, not the "
-                "%d of the last evaluate / map; evaluate the batch again"
-                % (self.ctx.n_prog, len(last)))
+        def own():
+            last = self._lex_batch[0]
+            if len(individuals) != len(last) or \
+                    any(a is not b for a, b in zip(individuals, last)):
+                raise ValueError(
+                    "select_lexicase: individuals must be the batch of this "
+                    "evaluator's last evaluate / map, the same objects in "
+                    "the same order: the GPU holds that batch's per-case "
+                    "errors")
+        last, results = self._last_batch(
+            "select_lexicase", True,
+            "this evaluator's last evaluate / map left no per-case matrix on "
+            "the GPU (its spec is %s; evaluate with SymbRegCaseAbsErrors, "
+            "SymbRegCaseErrors or BooleanCaseHits first)", own=own)
         for res in results:
             if isinstance(res, BaseException):
                 raise res
@@ -1610,16 +1592,64 @@ class GPUEvaluator(object):
         :class:`BooleanCaseHits` / :class:`TypedCaseHits` evaluation, read
         back from the device's bit matrix on request (either *cases* mode).  ``ValueError`` when the
         last evaluate / map left none (as :meth:`select_lexicase`)."""
-        if not getattr(self.spec, "hit_planes", False) or \
-                self._lex_batch is None:
-            raise ValueError(
-                "last_case_hits: this evaluator's last evaluate / map left "
-                "no hit planes on the GPU (its spec is %s; evaluate with "
-                "BooleanCaseHits first)" % type(self.spec).__name__)
-        n = len(self._lex_batch[0])
+        last, _ = self._last_batch(
+            "last_case_hits", getattr(self.spec, "hit_planes", False),
+            "this evaluator's last evaluate / map left no hit planes on the "
+            "GPU (its spec is %s; evaluate with BooleanCaseHits first)",
+            loaded=False)
+        n = len(last)
         if n == 0:
             return np.zeros((0, self.spec.n_cases), dtype=bool)
         return unpack_bitplanes(self.ctx.hit_planes(n), self.spec.n_cases)
+
+    def _last_batch(self, what, served, missing, eps=None, hits_eps=None,
+                    own=None, loaded=True):
+        """The batch of the last :meth:`evaluate` / :meth:`map` and its
+        results → ``(last, results)``, for the methods that read the
+        per-case matrix it left on the GPU.  ``ValueError``, in this order:
+        no such matrix — none at all, or not *served*: one of the kind the
+        caller reads — in the caller's words *missing*; an *eps* for hit
+        planes, which are thresholded already (*hits_eps*: the caller's
+        clause); *own*, the caller's own checks; with *loaded*, another batch
+        in the context since.  ``%s`` in the caller's words is the spec's
+        name."""
+        if self._lex_batch is None or not served:
+            raise ValueError("%s: %s" % (what, missing.replace(
+                "%s", type(self.spec).__name__)))
+        if eps is not None and getattr(self.spec, "hit_planes", False):
+            raise ValueError("%s: eps applies to SymbRegCaseAbsErrors; %s "
+                             "(got eps=%r)" % (what, hits_eps.replace(
+                                 "%s", type(self.spec).__name__), eps))
+        if own is not None:
+            own()
+        last, results = self._lex_batch
+        if loaded and self.ctx.n_prog != len(last):
+            raise ValueError(
+                "%s: the context now holds %d programs, not the %d of the "
+                "last evaluate / map; evaluate the batch again"
+                % (what, self.ctx.n_prog, len(last)))
+        return last, results
+
+    def _hit_eps(self, what, eps):
+        """The threshold a call on the hit matrix passes on: 0.0 for hit
+        planes, else *eps* (default ``spec.hit_eps``), ``>= 0``."""
+        if getattr(self.spec, "hit_planes", False):
+            return 0.0
+        eps = self.spec.hit_eps if eps is None else float(eps)
+        if not eps >= 0.0:
+            raise ValueError("%s: eps must be >= 0 (got %r)" % (what, eps))
+        return eps
+
+    def _raised(self, results):
+        """The indices of the individuals whose result is an exception
+        (found once per evaluation: a pass over a million results costs more
+        than a count on the GPU)."""
+        cache = getattr(self, "_group_raised", None)
+        if cache is None or cache[0] is not results:
+            cache = self._group_raised = (results, [
+                i for i, res in enumerate(results)
+                if isinstance(res, BaseException)])
+        return cache[1]
 
     def _group_masks(self, groups):
         """*groups* of :meth:`group_hits` as ``bool[G, n_cases]``."""
@@ -1668,19 +1698,11 @@ class GPUEvaluator(object):
         ``ValueError`` when the last evaluate / map left no hit planes (as
         :meth:`last_case_hits`) or another batch has been loaded since (as
         :meth:`select_lexicase`)."""
-        if not getattr(self.spec, "hit_planes", False) or \
-                self._lex_batch is None:
-            raise ValueError(
-                "group_hits: this evaluator's last evaluate / map left "
-                "no hit planes on the GPU (its spec is %s; evaluate with "
-                "BooleanCaseHits, TypedCaseHits, BooleanConfusion or "
-                "TypedConfusion first)" % type(self.spec).__name__)
-        last, results = self._lex_batch
-        if self.ctx.n_prog != len(last):
-            raise ValueError(
-                "group_hits: the context now holds %d programs, not the "
-                "%d of the last evaluate / map; evaluate the batch again"
-                % (self.ctx.n_prog, len(last)))
+        last, results = self._last_batch(
+            "group_hits", getattr(self.spec, "hit_planes", False),
+            "this evaluator's last evaluate / map left no hit planes on the "
+            "GPU (its spec is %s; evaluate with BooleanCaseHits, "
+            "TypedCaseHits, BooleanConfusion or TypedConfusion first)")
         masks = self._group_masks(groups)
         n, G = len(last), len(masks)
         out = np.zeros((n, G), dtype=np.int64)
@@ -1690,14 +1712,7 @@ class GPUEvaluator(object):
         for s in range(0, G, _lib.HIT_GROUPS_MAX):
             e = min(G, s + _lib.HIT_GROUPS_MAX)
             out[:, s:e] = self.ctx.hit_group_counts(None, 0, 0, planes[s:e])
-        # (who raised: found once per evaluation, a pass over a million
-        # results costs more than the count)
-        cache = getattr(self, "_group_raised", None)
-        if cache is None or cache[0] is not results:
-            cache = self._group_raised = (results, [
-                i for i, res in enumerate(results)
-                if isinstance(res, BaseException)])
-        out[cache[1]] = -1
+        out[self._raised(results)] = -1
         return out
 
     def _case_weights_batch(self, what, eps):
@@ -1705,42 +1720,22 @@ class GPUEvaluator(object):
         live)``: the batch's size, the threshold to pass on, the indices of
         the individuals whose result is an exception and the live mask
         (None when nobody raised)."""
-        bits = getattr(self.spec, "hit_planes", False)
-        if self._lex_batch is None or \
-                not (bits or getattr(self.spec, "abs_cases", False)):
-            raise ValueError(
-                "%s: this evaluator's last evaluate / map left no hit planes "
-                "and no per-case absolute errors on the GPU (its spec is %s; "
-                "evaluate with BooleanCaseHits, TypedCaseHits, "
-                "BooleanConfusion, TypedConfusion or SymbRegCaseAbsErrors "
-                "first)" % (what, type(self.spec).__name__))
-        if bits and eps is not None:
-            raise ValueError("%s: eps applies to SymbRegCaseAbsErrors; the "
-                             "cases of %s are hits already (got eps=%r)"
-                             % (what, type(self.spec).__name__, eps))
-        last, results = self._lex_batch
-        if self.ctx.n_prog != len(last):
-            raise ValueError(
-                "%s: the context now holds %d programs, not the "
-                "%d of the last evaluate / map; evaluate the batch again"
-                % (what, self.ctx.n_prog, len(last)))
-        if bits:
-            eps = 0.0
-        else:
-            eps = self.spec.hit_eps if eps is None else float(eps)
-            if not eps >= 0.0:
-                raise ValueError("%s: eps must be >= 0 (got %r)" % (what, eps))
-        cache = getattr(self, "_group_raised", None)
-        if cache is None or cache[0] is not results:
-            cache = self._group_raised = (results, [
-                i for i, res in enumerate(results)
-                if isinstance(res, BaseException)])
+        last, results = self._last_batch(
+            what, getattr(self.spec, "hit_planes", False) or
+            getattr(self.spec, "abs_cases", False),
+            "this evaluator's last evaluate / map left no hit planes and no "
+            "per-case absolute errors on the GPU (its spec is %s; evaluate "
+            "with BooleanCaseHits, TypedCaseHits, BooleanConfusion, "
+            "TypedConfusion or SymbRegCaseAbsErrors first)",
+            eps=eps, hits_eps="the cases of %s are hits already")
+        eps = self._hit_eps(what, eps)
+        raised = self._raised(results)
         live = None
-        if cache[1]:
+        if raised:
             alive = np.ones(len(last), dtype=bool)
-            alive[cache[1]] = False
+            alive[raised] = False
             live = _lib.pack_live_mask(alive)
-        return len(last), eps, cache[1], live
+        return len(last), eps, raised, live
 
     def case_solve_counts(self, eps=None):
         """``int64[n_cases]``: how many individuals of the last
