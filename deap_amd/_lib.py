@@ -124,6 +124,7 @@ SIGNATURES = {
     "gpe_debug_translate_mode": (_I, [_P, _I64, _P, _I64, _P, _I, _P, _I, _P,
                                          _I64, _P, _P, _P, _P, _I]),
     "gpe_debug_trig_classes_mode": (_I, [_P, _I64, _P, _P, _I, _I, _P, _I64]),
+    "gpe_debug_trig_picks": (_I, [_P, _I64, _P, _P, _I, _I, _P, _I64]),
     "gpe_last_trig_picked": (_I, [_P, ctypes.POINTER(ctypes.c_int64)]),
     "gpe_comm_unique_id": (_I, [_P]),
     "gpe_comm_init": (_I, [_P, _I, _I, _P]),
@@ -536,25 +537,37 @@ def host_lexicase_par(values, maximise, k, seed, mode=0, epsilon=0.0):
 
 
 TRIG_CLASSES = ("general", "mid", "small")
-# the classes GPE_TRIG_RANGES=2 (the default) picks handlers by
+# the classes GPE_TRIG_RANGES=2 and 3 (the default) pick handlers by
 TRIG_PICKED = TRIG_CLASSES + ("midlo", "wide")
+
+
+def _trig_pass(fn, words, lo, hi, mode):
+    """One of the library's two range-pass diagnostics over one program."""
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    lo = np.ascontiguousarray(lo, dtype=np.float64)
+    hi = np.ascontiguousarray(hi, dtype=np.float64)
+    assert lo.shape == hi.shape and lo.ndim == 1
+    out = np.zeros(max(len(words), 1), dtype=np.int32)
+    n = fn(_ptr(words), len(words), _ptr(lo), _ptr(hi), len(lo), int(mode), _ptr(out), len(out))
+    if n < 0:
+        raise GpeError("gpe_debug_trig_classes: malformed program or unknown mode")
+    return out[:n]
 
 
 def debug_trig_classes(words, lo, hi, mode=1):
     """Host-only: the range pass (csrc/trig_ranges.h) over one program's
     flattener words with column bounds lo[v], hi[v]: the class index of each
     sin/cos node, in word order.  ``mode`` 1: the base classes
-    (``TRIG_CLASSES``); 2, the library's default: ``TRIG_PICKED``."""
-    words = np.ascontiguousarray(words, dtype=np.uint32)
-    lo = np.ascontiguousarray(lo, dtype=np.float64)
-    hi = np.ascontiguousarray(hi, dtype=np.float64)
-    assert lo.shape == hi.shape and lo.ndim == 1
-    out = np.zeros(max(len(words), 1), dtype=np.int32)
-    n = load().gpe_debug_trig_classes_mode(_ptr(words), len(words), _ptr(lo), _ptr(hi),
-                                       len(lo), int(mode), _ptr(out), len(out))
-    if n < 0:
-        raise GpeError("gpe_debug_trig_classes: malformed program")
-    return out[:n]
+    (``TRIG_CLASSES``); 2: ``TRIG_PICKED``, midlo a cos class.  (This entry
+    point's contract stops at mode 2; mode 3: ``debug_trig_picks``.)"""
+    return _trig_pass(load().gpe_debug_trig_classes_mode, words, lo, hi, mode)
+
+
+def debug_trig_picks(words, lo, hi, mode=3):
+    """``debug_trig_classes`` for every mode of the pass: 1, 2, 3, the
+    library's default — mode 2's classes with midlo for a sin node too — and
+    4 (mode 2's classes; mode 3's handlers in ``debug_translate``)."""
+    return _trig_pass(load().gpe_debug_trig_picks, words, lo, hi, mode)
 
 
 def debug_translate(batch, nv, table, bounds=None, mode=1):

@@ -368,13 +368,15 @@ struct gpe_ctx {
   int exact_all = 1;           // GPE_EXACT_ALL: the exact cores (0: table cores + redo)
   // range-specialised sin/cos handlers of the exact cores (trig_ranges.h;
   // GPE_TRIG_RANGES=0: only the general handlers; 1: SIN/COS_MID and _SMALL,
-  // the A/B control of the later ones; 2, the default: all — trig_ranges::
-  // Mode).  The F machine's column bounds, (lo, hi) per column of
+  // the A/B control of the later ones; 2: all; 3, the default: all, sin
+  // MIDLO, and the MID / MIDLO bodies with static lane roles, 2 being their
+  // A/B control and 4 (3 without the sin MIDLO pick) SIN_MIDLO3's —
+  // trig_ranges::Mode).  The F machine's column bounds, (lo, hi) per column of
   // [0, 3 nv_user) (the trig leaves' columns included), set and reset by
   // gpe_set_cases; the sin/cos words of the last exact-core translation: by
   // base class (general, mid, small), then by the class picked (general, mid,
   // small, midlo, wide)
-  int trig_ranges = 2;
+  int trig_ranges = 3;
   std::vector<double> col_bnd;
   double* d_col_bnd = nullptr;
   unsigned long long* d_trig_cls = nullptr;

@@ -1569,13 +1569,52 @@ class Gen(object):
         "wide" (every lane finite and |x| < 1e8 < 105414350): the general
         body without the VRED update (VRED is read for the inf/nan exit and
         the __branred test, neither of which such a lane can need), the
-        105414350 compare, its branch and the slow path."""
+        105414350 compare, its branch and the slow path.
+        "mid3", "midlo3" (GPE_TRIG_RANGES=3; "mid" and "midlo" stay as they
+        are, mode 2's, the A/B control): "mid" / "midlo" without the all-lane
+        da.  The class fixes the lane roles — cos: do_cos(x, 0) in exactly
+        the small lanes, do_sin(a, da) in exactly the d lanes; sin:
+        do_sin(x, 0) in the small lanes, do_cos(t, hp1) in the d lanes — so
+        da is written and read under the d mask only: no zeroing move, no
+        small-lane v = xr + da (da = 0: an identity add) and da := v.  The
+        all-lane fma(m, p, da) becomes one masked fma per role with the
+        operands each lane had (nothing to prove).  cos: the do_cos block
+        moves below the polynomial's first operations (w first, so that p
+        takes xx's registers and the VGPR count stays) and takes the fma
+        with addend xr, the do_sin block the one with addend da, both into
+        m's registers; "midlo3" drops da's sign operation (a > 0.13), "mid3"
+        keeps it inside the d block.  sin: the d lanes form v = xr + dx
+        themselves (dx = hp1, negated where t < 0: the move and its sign
+        operation inside the d block), the fma runs for all lanes with
+        addend xr (the do_cos lanes' s), and the small lanes then take
+        SMALL's pieces: s = m p + xr, no fma(da, xr, w), TAYLOR_SIN without
+        0.5 da and + da.  These differ from the terms with da = +-0 at most
+        in a zero's sign, which the following + xr / |x| + q absorbs, and
+        xr + 0 = xr needs xr != -0: the argument of "small" above.  sin
+        "midlo3" (a new pick, |x| < 1.44 < pi/2: trig_ranges.h kMidLo): t =
+        hp0 - |x| > 0.13 in every d lane, dx = hp1 is the SGPR pair itself
+        and no da register exists; TAYLOR_SIN stays (the small lanes').
+        tests/test_asm_emu_mid_noda.py executes all four on both exact cores
+        with poisoned temporaries: bit equality with the host libm and with
+        the mode-2 bodies on zeros, denormals, every binade, both sides of the
+        0.126, 0.85546875, pi/2, 1.44 and 2.42 edges, 2.426265 from below
+        ("mid3" up to the last double under it; at and past it a lane is
+        reduce_sincos's, which no MID body has) and NaN lanes."""
         assert self.K == 2 and GLIBC4
-        assert rng in (None, "mid", "small", "midlo", "wide") and \
-            (rng is None or self.salu)
+        assert rng in (None, "mid", "small", "midlo", "wide", "mid3", "midlo3") \
+            and (rng is None or self.salu)
         cos = want == "cos"
+        # nd: the bodies with static lane roles ("mid3", "midlo3"), no
+        # all-lane da
+        nd, tag = rng in ("mid3", "midlo3"), rng
+        if nd:
+            rng = rng[:-1]
         midlo, wide = rng == "midlo", rng == "wide"
-        assert cos or not midlo
+        assert cos or nd or not midlo
+        # sin "midlo3": "mid3" with t = hp0 - |x| > 0 proven, hp1 an SGPR
+        # operand (TAYLOR_SIN stays: its lanes are the small ones)
+        hp1s = midlo and not cos
+        midlo = midlo and cos
         mid, small = rng in ("mid", "midlo"), rng == "small"
         known = mid or small             # (wide: the general body's range tests)
         seq = []
@@ -1591,7 +1630,7 @@ class Gen(object):
         SK = self.SCONST if self.m0lane else SSAVE
         assert not (self.prefetch and not self.m0lane)
         S = GLIBC_SPLIT_S
-        W = "%s_%%=" % (want + ("_" + rng if rng else ""))
+        W = "%s_%%=" % (want + ("_" + tag if tag else ""))
         N = ["{nn_lo}", "{nn_hi}"]
 
         def const(name):
@@ -1616,13 +1655,21 @@ class Gen(object):
                 a(k, "v_add_f64 {%sy}, @HP0@, -|{x}|" % pfx, [pfx + "y"], ["x"])
                 a(k, "v_add_f64 {x}, {%sy}, @HP1@" % pfx, [], [pfx + "y"])
                 a(k, "v_add_f64 {da}, {%sy}, -{x}" % pfx, ["da"],
-                  [pfx + "y", "x", "da"])
+                  [pfx + "y", "x"] + ([] if nd else ["da"]))
                 a(k, "v_add_f64 {da}, {da}, @HP1@", ["da"], ["da"])
+                if nd and not midlo:     # (midlo: a > 0.13, da's sign stays)
+                    a(k, "v_bitop3_b32 {da_hi}, {da_hi}, {x_hi}, %s bitop3:0x78" % SC,
+                      ["da"], ["x", "da"])
             else:
                 if not known:            # (mid: set for all lanes before)
                     a(k, "v_mov_b32_e32 %s, {x_hi}" % N[k], ["nn"], ["x", "nn"])
                 a(k, "v_add_f64 {x}, @HP0@, -|{x}|", [], ["x"])
-                a(k, "v_mov_b64_e32 {da}, @HP1@", ["da"], ["da"])
+                if hp1s:                 # (t > 0: v = xr + hp1, no da register)
+                    return
+                a(k, "v_mov_b64_e32 {da}, @HP1@", ["da"], [] if nd else ["da"])
+                if nd:                   # (t < 0 past pi/2: do_cos negates dx)
+                    a(k, "v_bitop3_b32 {da_hi}, {da_hi}, {x_hi}, %s bitop3:0x78" % SC,
+                      ["da"], ["x", "da"])
 
         def eblock(k, pfx):
             """2.426265 <= |x| < 105414350: reduce_sincos; n = the quadrant
@@ -1804,11 +1851,19 @@ class Gen(object):
                           ["x"] + (["nn"] if k else []))
             if small:                    # (da = +-0 drops out of every term)
                 return
-            both("v_mov_b64_e32 {da}, 0", ["da"], [])
+            if not nd:                   # (nd: da lives in the d lanes only)
+                both("v_mov_b64_e32 {da}, 0", ["da"], [])
             # 0.85546875 as a double (0x3feb6000 : 0) in the free pair SP
             a(0, "s_mov_b32 %s, 0\ns_mov_b32 s%d, s%d" % (SC, self.SM0, SSAVE))
             for k in range(2):
                 a(k, "v_cmp_gt_f64_e64 %s, %s, |{x}|" % (M[k], SP), [], ["x"])
+            if nd:
+                # the sign mask, for the d blocks to sign da with.  SC is the
+                # low word of the 0.85546875 pair the two compares above
+                # read: this write must stay after both in program order
+                # (chain 1's entry, emitted after chain 1's compare; a wave
+                # issues in order, so they have read the pair by then)
+                a(1, "s_brev_b32 %s, 1" % SC)
             for k in range(2):
                 lab = ".Lmd%d_%s" % (k, W)
                 # d = the handler's lanes that are not small (sin: the do_cos
@@ -1830,8 +1885,9 @@ class Gen(object):
         # do_sin lanes' TAYLOR_SIN takes (|a|, that dx) and is odd in (a, da)
         if self.prio and self.prio_late and TRIG_DROP == "join":
             a(0, "s_setprio %d" % self.prio[1])
-        a(0, "s_brev_b32 %s, 1" % SC)
-        if not small:
+        if not nd:
+            a(0, "s_brev_b32 %s, 1" % SC)
+        if not small and not nd:
             both("v_bitop3_b32 {da_hi}, {da_hi}, {x_hi}, %s bitop3:0x78" % SC,
                  ["da"], ["x", "da"])
         both("v_add_f64 {u}, |{x}|, @BIG@", ["u"], ["x"])
@@ -1841,29 +1897,62 @@ class Gen(object):
         # do_cos lanes: entries B[i], NA[i]; v = xr + dx (into xr), dx := v
         # (s = v + v xx p)
         # (small: sin has no do_cos lanes; cos has no others, EXEC stays)
-        for k in range(0 if small and not cos else 2):
+        # nd: the class fixes the lane roles (cos: do_cos = the small lanes,
+        # v = xr + 0 = xr; sin: do_cos = the d lanes, v = xr + dx with dx =
+        # hp1 signed as t), so dx exists in the d lanes only and the all-lane
+        # fma(m, p, dx) is one masked fma per role, each lane's operation
+        # unchanged.  cos: in the do_cos block, moved below the polynomial's
+        # first operations, with addend xr, and in the do_sin block with
+        # addend da, both into m's register.  sin: for all lanes with addend
+        # xr (the do_cos lanes' value); the do_sin lanes then take SMALL's
+        # m p + xr in their block
+        def bc_block(k):
             lab = ".Lbc%d_%s" % (k, W)
             if not small:
                 a(k, "s_mov_b64 exec, %s\ns_cbranch_execz %s" % (M[k], lab))
             a(k, "v_add_u32_e32 {adr0}, 0x%x, {adr0}" % S, ["adr0"], ["adr0"])
-            if not small:                # (small: v = xr + (+-0) = xr, >= +0)
+            if nd and cos:               # (s = v + v xx p, v = xr)
+                a(k, "v_fma_f64 {m}, {m}, {p}, {xr}", ["m"], ["m", "p", "xr"])
+                a(k, lab + ":")
+            elif nd:
+                a(k, "v_add_f64 {xr}, {xr}, %s" % ("@HP1@" if hp1s else "{da}"),
+                  ["xr"], ["xr"] + ([] if hp1s else ["da"]))
+                a(k, lab + ":")
+            elif not small:              # (small: v = xr + (+-0) = xr, >= +0)
                 a(k, "v_add_f64 {xr}, {xr}, {da}", ["xr"], ["xr", "da"])
                 a(k, "v_mov_b64_e32 {da}, {xr}", ["da"], ["xr", "da"])
                 a(k, lab + ":")
-        if not small:
-            a(1, "s_mov_b64 exec, %s" % SV)
+        sv = "m" if nd and cos else "s"  # (the variable that holds s)
+        if not (nd and cos):
+            for k in range(0 if small and not cos else 2):
+                bc_block(k)
+            if not small:
+                a(1, "s_mov_b64 exec, %s" % SV)
+        def w_poly():
+            both("v_fma_f64 {w}, {xx}, @CS6@, @CS4@", ["w"], ["xx"])
+            both("v_fma_f64 {w}, {w}, {xx}, @CS2@", ["w"], ["w", "xx"])
+            both("v_mul_f64 {w}, {w}, {xx}", ["w"], ["w", "xx"])
         both("v_mul_f64 {xx}, {xr}, {xr}", ["xx"], ["xr"])
+        if nd:
+            # (m and p live on into the role blocks: w first, so that p takes
+            # xx's registers and the core's VGPR count stays)
+            w_poly()
         both("v_mul_f64 {m}, {xr}, {xx}", ["m"], ["xr", "xx"])
         both("v_fma_f64 {p}, {xx}, @SN5@, @SN3@", ["p"], ["xx"])
-        if small and cos:                # (do_cos: s = v + v xx p with v = xr)
+        if nd and cos:                   # (in the two role blocks)
+            pass
+        elif (small and cos) or nd:      # (do_cos: s = v + v xx p with v = xr)
             both("v_fma_f64 {s}, {m}, {p}, {xr}", ["s"], ["m", "p", "xr"])
         elif small:                      # (do_sin: dx = +-0; + xr follows)
             both("v_mul_f64 {s}, {m}, {p}", ["s"], ["m", "p"])
         else:
             both("v_fma_f64 {s}, {m}, {p}, {da}", ["s"], ["m", "p", "da"])
-        both("v_fma_f64 {w}, {xx}, @CS6@, @CS4@", ["w"], ["xx"])
-        both("v_fma_f64 {w}, {w}, {xx}, @CS2@", ["w"], ["w", "xx"])
-        both("v_mul_f64 {w}, {w}, {xx}", ["w"], ["w", "xx"])
+        if not nd:
+            w_poly()
+        if nd and cos:
+            for k in range(2):
+                bc_block(k)
+            a(1, "s_mov_b64 exec, %s" % SV)
         both("ds_read_b128 {EA}, {adr0} offset:0", ["EA"], ["adr0"])
         both("ds_read_b128 {EB}, {adr0} offset:%d" % S, ["EB"], ["adr0"])
         if os.environ.get("GEN_ASM_EXPERIMENT") == "dup_tab":
@@ -1899,8 +1988,16 @@ class Gen(object):
             else:
                 a(k, "s_andn2_b64 exec, %s, %s\ns_mov_b64 %s, %s\ns_cbranch_scc0 %s"
                   % (SV, M[k], M[k], SV, lab))
-            a(k, "v_add_f64 {s}, {s}, {xr}", ["s"], ["s", "xr"])
-            if not small:                # (small: dx xr = +-0, w >= +0)
+            if nd and cos:               # (dx + xr xx p: the d lanes' da)
+                a(k, "v_fma_f64 {m}, {m}, {p}, {da}", ["m"], ["m", "p", "da"])
+                a(k, "v_add_f64 {m}, {m}, {xr}", ["m"], ["m", "xr"])
+            elif nd:                     # (SMALL's do_sin: dx = +-0)
+                a(k, "v_mul_f64 {s}, {m}, {p}", ["s"], ["m", "p", "s"])
+                a(k, "v_add_f64 {s}, {s}, {xr}", ["s"], ["s", "xr"])
+            else:
+                a(k, "v_add_f64 {s}, {s}, {xr}", ["s"], ["s", "xr"])
+            # (small, and nd's sin: dx xr = +-0, w >= +0)
+            if not small and not (nd and not cos):
                 a(k, "v_fma_f64 {w}, {da}, {xr}, {w}", ["w"], ["da", "xr", "w"])
             if not known or cos:
                 a(k, "v_bitop3_b32 %s, %s, {x_hi}, %s bitop3:0x78" % (N[k], N[k], SC),
@@ -1924,7 +2021,7 @@ class Gen(object):
             a(k, "v_fma_f64 {pt}, {pt}, {xx2}, @S3@", ["pt"], ["pt", "xx2"])
             a(k, "v_fma_f64 {pt}, {pt}, {xx2}, @S2@", ["pt"], ["pt", "xx2"])
             a(k, "v_fma_f64 {pt}, {pt}, {xx2}, @S1@", ["pt"], ["pt", "xx2"])
-            if small:                    # (dx = +-0: 0.5 dx and + dx drop out)
+            if small or (nd and not cos):    # (dx = +-0: 0.5 dx and + dx drop out)
                 a(k, "v_mul_f64 {q}, {pt}, |{x}|", ["q"], ["pt", "x"])
                 a(k, "v_mul_f64 {q}, {q}, {xx2}", ["q"], ["q", "xx2"])
             else:
@@ -1939,9 +2036,9 @@ class Gen(object):
         allt = cs or midlo               # (the table result is every lane's)
         if self.prio and self.prio_late and TRIG_DROP == "wait":
             a(1, "s_setprio %d" % self.prio[1])
-        both("v_fma_f64 {cor}, {s}, {TBb}, {TAa}", ["cor"], ["s", "EB", "EA"])
+        both("v_fma_f64 {cor}, {%s}, {TBb}, {TAa}" % sv, ["cor"], [sv, "EB", "EA"])
         both("v_fma_f64 {cor}, -{w}, {TA}, {cor}", ["cor"], ["w", "EA", "cor"])
-        both("v_fma_f64 {cor}, {s}, {TB}, {cor}", ["cor"], ["s", "EB", "cor"])
+        both("v_fma_f64 {cor}, {%s}, {TB}, {cor}" % sv, ["cor"], [sv, "EB", "cor"])
         for k in range(2):
             if not allt:
                 a(k, "s_mov_b64 exec, %s" % M[k])
@@ -2704,11 +2801,13 @@ class Gen(object):
     # picks them per node
     RANGE_HANDLERS = [("sin", "mid"), ("cos", "mid"), ("sin", "small"),
                       ("cos", "small"), ("cos", "midlo"), ("sin", "wide"),
-                      ("cos", "wide")]
+                      ("cos", "wide"), ("sin", "mid3"), ("cos", "mid3"),
+                      ("sin", "midlo3"), ("cos", "midlo3")]
 
     def range_handlers(self):
         """SIN_MID, COS_MID, SIN_SMALL, COS_SMALL, COS_MIDLO, SIN_WIDE,
-        COS_WIDE.  The exact cores with
+        COS_WIDE, then mode 3's SIN_MID3, COS_MID3, SIN_MIDLO3, COS_MIDLO3
+        (the ids of a layout only ever grow at the end).  The exact cores with
         glibc_seq4's default scheme carry the specialised bodies
         (glibc_seq4(rng=...)); in every other core the ids alias the general
         handler: an entry of their own (every table offset is distinct and
@@ -3016,6 +3115,10 @@ class Gen(object):
                "H_COS_MIDLO": ids.get("COS_MIDLO", -1),
                "H_SIN_WIDE": ids.get("SIN_WIDE", -1),
                "H_COS_WIDE": ids.get("COS_WIDE", -1),
+               "H_SIN_MID3": ids.get("SIN_MID3", -1),
+               "H_COS_MID3": ids.get("COS_MID3", -1),
+               "H_SIN_MIDLO3": ids.get("SIN_MIDLO3", -1),
+               "H_COS_MIDLO3": ids.get("COS_MIDLO3", -1),
                "H_COUNT": len(names), "WINDOW": WINDOW,
                "SGPR_BASE": self.BASE,
                "LIM_HI": LIM_HI, "FAST_HI": FAST_HI}

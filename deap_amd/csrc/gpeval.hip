@@ -546,6 +546,15 @@ struct CoreIds {
   // cores without specialised bodies alias SIN / COS there
   int H_TRIG[trig_ranges::kClasses][2] = {{-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}};
   int H_ABS = -1, H_SQRT = -1;      // every core but the typed one
+  // trig_ranges::kStatic's handlers of the classes mid and midlo (the bodies
+  // with static lane roles; midlo is a sin class too there)
+  int H_MID3[2] = {-1, -1}, H_MIDLO3[2] = {-1, -1};
+  constexpr int trig(int cls, bool cos, int mode) const {
+    return mode < trig_ranges::kStatic   ? H_TRIG[cls][cos]
+           : cls == trig_ranges::MID     ? H_MID3[cos]
+           : cls == trig_ranges::MIDLO   ? H_MIDLO3[cos]
+                                         : H_TRIG[cls][cos];
+  }
 };
 #define CORE_IDS(NS)                                                          \
   CoreIds {                                                                   \
@@ -561,7 +570,13 @@ struct CoreIds {
 static_assert(asmcore::H_SIN_MID == asmcore::H_COS + 1 &&
                   asmcore::H_COS_SMALL == asmcore::H_COS + 4 &&
                   asmcore::H_COS_MIDLO == asmcore::H_COS + 5 &&
-                  asmcore::H_COS_WIDE == asmcore::H_COUNT - 1 &&
+                  asmcore::H_COS_WIDE == asmcore::H_COS + 7 &&
+                  asmcore::H_SIN_MID3 == asmcore::H_COS + 8 &&
+                  asmcore::H_COS_MIDLO3 == asmcore::H_COUNT - 1 &&
+                  asmcore_exact::H_COS_MIDLO3 == asmcore::H_COS_MIDLO3 &&
+                  asmcore_exact_deep::H_COS_MIDLO3 == asmcore_deep::H_COS_MIDLO3 &&
+                  asmcore32::H_COS_MIDLO3 == asmcore::H_COS_MIDLO3 &&
+                  asmcore32_deep::H_COS_MIDLO3 == asmcore_deep::H_COS_MIDLO3 &&
                   asmcore_exact::H_SIN_MID == asmcore::H_SIN_MID &&
                   asmcore_exact::H_COS_WIDE == asmcore::H_COS_WIDE &&
                   asmcore_exact_deep::H_SIN_MID == asmcore_deep::H_SIN_MID &&
@@ -574,6 +589,10 @@ static_assert(asmcore::H_SIN_MID == asmcore::H_COS + 1 &&
     CoreIds c = CORE_IDS(NS);       \
     c.H_ABS = NS::H_ABS;            \
     c.H_SQRT = NS::H_SQRT;          \
+    c.H_MID3[0] = NS::H_SIN_MID3;   \
+    c.H_MID3[1] = NS::H_COS_MID3;   \
+    c.H_MIDLO3[0] = NS::H_SIN_MIDLO3; \
+    c.H_MIDLO3[1] = NS::H_COS_MIDLO3; \
     return c;                       \
   }()
 constexpr CoreIds kIds = CORE_IDS_F(asmcore);
@@ -676,7 +695,7 @@ __global__ __launch_bounds__(256) void const_hits(const uint32_t* kc, int64_t n,
 // the host (gpe_debug_translate, tests) and in translate_kernel.
 // `bnd` (the exact cores, while writing): the case columns' (lo, hi), nb of
 // them — every sin/cos word is then the handler of its argument's proven
-// range (trig_ranges.h; `mode`: kBase or kAll), counted into `cls` when given
+// range (trig_ranges.h; `mode`: kBase, kAll or kStatic), counted into `cls` when given
 // (kTrigCounts words: the base classes general, mid, small, then the words
 // per class picked); null: every sin/cos is the general handler.  The word
 // count is the same.
@@ -746,7 +765,7 @@ HD int64_t translate_words(const uint32_t* w, const uint32_t* tab, const CoreIds
     if (ranges) {
       const int c = R.step(word, konst ? w[0] : 0u, konst ? w[1] : 0u);
       if (c >= 0) {
-        h = I.H_TRIG[c][op == OP_COS ? 1 : 0];
+        h = I.trig(c, op == OP_COS, mode);
         if (cls) {
           ++cls[R.base];
           ++cls[3 + c];
@@ -1789,7 +1808,9 @@ int gpe_create(int device, gpe_ctx** out) {
   if ((env = getenv("GPE_EXACT_ALL"))) ctx->exact_all = atoi(env) != 0;
   if ((env = getenv("GPE_TRIG_RANGES")))
     ctx->trig_ranges = atoi(env) <= 0 ? trig_ranges::kOff
-                       : atoi(env) == 1 ? trig_ranges::kBase : trig_ranges::kAll;
+                       : atoi(env) == 1 ? trig_ranges::kBase
+                       : atoi(env) == 2 ? trig_ranges::kAll
+                       : atoi(env) == 4 ? trig_ranges::kStaticMid : trig_ranges::kStatic;
   if ((env = getenv("GPE_REDO_EXP")) && atoi(env) >= 14 && atoi(env) <= 40)
     ctx->redo_hi = (uint32_t)(0x3ff + atoi(env)) << 20;
   if ((env = getenv("GPE_REDO_EXP_DEEP")) && atoi(env) >= 14 && atoi(env) <= 40)
@@ -4024,7 +4045,7 @@ int gpe_debug_translate_mode(const uint32_t* code, int64_t n_words,
                                 int64_t* starts, int64_t* n_out, const double* lo,
                                 const double* hi, int mode) {
   if ((lo == nullptr) != (hi == nullptr)) return GPE_E_INVALID;
-  if (mode != trig_ranges::kBase && mode != trig_ranges::kAll) return GPE_E_INVALID;
+  if (mode < trig_ranges::kBase || mode > trig_ranges::kStaticMid) return GPE_E_INVALID;
   std::vector<double> bnd;
   if (lo)
     for (int v = 0; v < nv; ++v) {
@@ -4063,8 +4084,14 @@ int gpe_debug_trig_classes(const uint32_t* code, int64_t n_words, const double* 
 
 int gpe_debug_trig_classes_mode(const uint32_t* code, int64_t n_words, const double* lo,
                             const double* hi, int nv, int mode, int32_t* out, int64_t cap) {
+  if (mode != trig_ranges::kBase && mode != trig_ranges::kAll) return -1;
+  return gpe_debug_trig_picks(code, n_words, lo, hi, nv, mode, out, cap);
+}
+
+int gpe_debug_trig_picks(const uint32_t* code, int64_t n_words, const double* lo,
+                         const double* hi, int nv, int mode, int32_t* out, int64_t cap) {
   if (!code || n_words <= 0 || nv < 0 || (nv && (!lo || !hi)) || (cap && !out) || cap < 0 ||
-      (mode != trig_ranges::kBase && mode != trig_ranges::kAll))
+      mode < trig_ranges::kBase || mode > trig_ranges::kStaticMid)
     return -1;
   std::vector<double> bnd;
   for (int v = 0; v < nv; ++v) {

@@ -17,8 +17,8 @@
 // "tainted", every arithmetic result computed from it is tainted, and a
 // tainted argument is class general.
 //
-// The third state, "nanable" (kAll only): every lane is finite and inside the
-// bounds, or NaN.  sin/cos of a tainted argument is nanable within [-1, 1]:
+// The third state, "nanable" (kAll and kStatic): every lane is finite and
+// inside the bounds, or NaN.  sin/cos of a tainted argument is nanable within [-1, 1]:
 // the general handler returns glibc's value for a finite lane and NaN for an
 // inf or nan one (x - x).  The state is closed under add, sub, mul, neg
 // (a NaN operand gives NaN; finite operands inside their bounds give a
@@ -67,17 +67,26 @@
 namespace trig_ranges {
 
 // GENERAL, MID, SMALL: the base classes (kBase picks only these); MIDLO (cos
-// only) and WIDE: kAll's.  The numbering is the ABI's (gpe_last_trig_classes)
+// only; kStatic: sin too) and WIDE: kAll's and kStatic's.  The numbering is
+// the ABI's (gpe_last_trig_classes)
 enum Class { GENERAL = 0, MID = 1, SMALL = 2, MIDLO = 3, WIDE = 4, kClasses = 5 };
-// GPE_TRIG_RANGES: 0 general handlers only (no pass), 1 the base classes, 2 all
-enum Mode { kOff = 0, kBase = 1, kAll = 2 };
+// GPE_TRIG_RANGES: 0 general handlers only (no pass), 1 the base classes, 2 all,
+// 3 (the default) all, MIDLO for sin too, and the MID / MIDLO handlers whose
+// lane roles are static (gen_asm.py glibc_seq4(rng="mid3" / "midlo3")): the
+// classes of a cos node and the values' intervals and states are mode 2's;
+// 4: mode 3 without the sin MIDLO pick (mode 2's classes, mode 3's bodies:
+// such a sin node is SIN_MID3's) — the A/B control of SIN_MIDLO3 alone
+enum Mode { kOff = 0, kBase = 1, kAll = 2, kStatic = 3, kStaticMid = 4 };
 constexpr int kSlots = 12;              // operand-stack slots (the deep cores' D)
 // class thresholds on m = max(|lo|, |hi|): deliberately below glibc's own
 // (|x| < 0.85546875: hx < 0x3feb6000; |x| < 2.426265...: hx < 0x400368fd)
 constexpr double kSmall = 0.855, kMid = 2.42;
 // cos, |x| < kMidLo: the do_sin lanes (0.85546875 <= |x|) have the argument
 // a = (hp0 - |x|) + hp1 > pi/2 - 1.44 = 0.13080 > 0.126, TAYLOR_SIN's bound:
-// a margin of 0.0048, against two roundings of 2^-53 relative
+// a margin of 0.0048, against two roundings of 2^-53 relative.  sin (kStatic),
+// |x| < kMidLo < pi/2: the do_cos lanes (0.85546875 <= |x|) have t = hp0 - |x|
+// > 0.13 > 0, so do_cos(t, hp1) never negates hp1: it is an operand, not a
+// register
 constexpr double kMidLo = 1.44;
 // |x| < kWide, clean: below __branred's 105414350 (hx < 0x419921fb) by 5 %
 constexpr double kWide = 1e8;
@@ -155,14 +164,15 @@ TR_HD inline Iv pdiv(const Iv& n, const Iv& d, bool np) {
   return q;
 }
 
-// The class of a sin (cos) node from its argument; `mode` kBase or kAll.
+// The class of a sin (cos) node from its argument; `mode` kBase, kAll or
+// kStatic.
 TR_HD inline int classify(const Iv& a, bool cos, int mode) {
   if (a.st == TAINT) return GENERAL;
   const double m = maxd(absd(a.lo), absd(a.hi));
   if (m < kSmall) return SMALL;
-  if (mode == kAll && cos && m < kMidLo) return MIDLO;
+  if ((mode == kStatic || (mode >= kAll && cos)) && m < kMidLo) return MIDLO;
   if (m < kMid) return MID;
-  return mode == kAll && a.st == CLEAN && m < kWide ? WIDE : GENERAL;
+  return mode >= kAll && a.st == CLEAN && m < kWide ? WIDE : GENERAL;
 }
 // The class kBase gives the same node (a value is clean exactly when kBase
 // calls it untainted, with the same bounds: nanable values never turn clean)
@@ -184,7 +194,7 @@ TR_HD inline double sin_ub(double t) {
 // (a tainted argument, kAll: finite lanes give a value in [-1, 1], inf and
 // nan lanes NaN — nanable; kBase: tainted)
 TR_HD inline Iv sin_iv(const Iv& a, int mode) {
-  if (a.st == TAINT) return mode == kAll ? mk(-1.0, 1.0, NANABLE) : taint();
+  if (a.st == TAINT) return mode >= kAll ? mk(-1.0, 1.0, NANABLE) : taint();
   if (a.lo < -1.5 || a.hi > 1.5) return mk(-1.0, 1.0, a.st);
   // on [-1.5, 1.5] sin is odd and has the sign of its argument (glibc's
   // too: it computes sin |x| and restores the sign)
@@ -194,7 +204,7 @@ TR_HD inline Iv sin_iv(const Iv& a, int mode) {
 // 1 - m^2/2 (>= 0.21 there); narrowed by a relative 2^-40 for glibc's ulp
 // and this evaluation's roundings, as above.
 TR_HD inline Iv cos_iv(const Iv& a, int mode) {
-  if (a.st == TAINT) return mode == kAll ? mk(-1.0, 1.0, NANABLE) : taint();
+  if (a.st == TAINT) return mode >= kAll ? mk(-1.0, 1.0, NANABLE) : taint();
   const double m = maxd(absd(a.lo), absd(a.hi));
   if (m > 1.25) return mk(-1.0, 1.0, a.st);
   return mk((1.0 - m * m * 0.5) * (1.0 - 0x1p-40), 1.0, a.st);

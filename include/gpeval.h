@@ -932,7 +932,13 @@ int gpe_last_trig_classes(const gpe_ctx* ctx, int64_t* out);
  * (every lane finite and |x| < 1e8: SIN_WIDE, COS_WIDE, the last two
  * entries), and a sin/cos over a possibly non-finite value is bounded by
  * [-1, 1] "or NaN", which mid, small and midlo accept (csrc/trig_ranges.h).
- * Any other mode: an error. */
+ * gpe_debug_translate_mode also takes 3, the library's default: mode 2 with
+ * midlo for a sin node too, and for mid and midlo the handlers with static
+ * lane roles (SIN_MID3, COS_MID3, SIN_MIDLO3, COS_MIDLO3, the table's last
+ * four entries), and 4: mode 2's classes with mode 3's handlers (a sin node
+ * below 1.44 stays mid: SIN_MID3), the A/B control of SIN_MIDLO3.  The classes
+ * of those modes: gpe_debug_trig_picks, which takes 1 to 4.  Any other mode:
+ * an error. */
 int gpe_debug_translate_mode(const uint32_t* code, int64_t n_words,
                                 const int64_t* off, int64_t n_prog,
                                 const int32_t* depth, int nv, const uint32_t* table,
@@ -941,13 +947,16 @@ int gpe_debug_translate_mode(const uint32_t* code, int64_t n_words,
                                 const double* hi, int mode);
 int gpe_debug_trig_classes_mode(const uint32_t* code, int64_t n_words, const double* lo,
                             const double* hi, int nv, int mode, int32_t* out, int64_t cap);
+int gpe_debug_trig_picks(const uint32_t* code, int64_t n_words, const double* lo,
+                         const double* hi, int nv, int mode, int32_t* out, int64_t cap);
 
 /* The sin/cos words of the last exact-core translation by the class whose
  * handler was picked: out[0] general, out[1] mid, out[2] small, out[3] midlo,
  * out[4] wide; their sum is that of gpe_last_trig_classes, which keeps
  * counting the base classes (GPE_TRIG_RANGES=1's choice) in every mode.
  * GPE_TRIG_RANGES=1: out[3] = out[4] = 0 and the rest is
- * gpe_last_trig_classes'. */
+ * gpe_last_trig_classes'.  GPE_TRIG_RANGES=3, the default: out[3] counts the
+ * sin nodes picked midlo too (mode 2 counts them mid). */
 int gpe_last_trig_picked(const gpe_ctx* ctx, int64_t* out);
 
 /* Diagnostic: evaluate the device's sin (fn 0), cos (fn 1), square (fn 2),

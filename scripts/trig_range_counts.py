@@ -5,16 +5,18 @@ arguments (tests/asm_emu.py on the CPU; no GPU).
 
 The first ``trees`` trees of the headline population (bench.py's seed and
 depths) are flattened; the range pass (csrc/trig_ranges.h, through
-gpe_debug_trig_classes) classifies every sin/cos node from the columns'
-bounds [-1, 1]; the words are evaluated on the first ``tiles`` 128-case tiles
-of the headline cases, and every sin/cos call's 128 arguments (chain k =
-cases 64k .. 64k + 63) run through the general handler and through the
-handler of the node's class, once with the base classes (GPE_TRIG_RANGES=1)
-and once with all of them (2, the default).  Prints, per mode and handler, the
-executed VALU (of them fp64), SALU and LDS instructions per wave-call, the
-class shares, and the weighted per-call totals of the specialised mix against
-the general handler alone, then the two modes side by side.  Every result is checked bit for bit against the host libm,
-and every argument against its class's range.
+gpe_debug_trig_picks) classifies every sin/cos node from the columns' bounds
+[-1, 1]; the words are evaluated on the first ``tiles`` 128-case tiles of the
+headline cases, and every sin/cos call's 128 arguments (chain k = cases
+64k .. 64k + 63) run through the general handler and through the handler of
+the node's class, three times: with the base classes (GPE_TRIG_RANGES=1),
+with all of them (2), and with the static-role MID / MIDLO bodies (3, the
+default).  Prints, per mode and handler, the executed VALU (of them fp64),
+SALU and LDS instructions per wave-call, the class shares, and the weighted
+per-call totals of the specialised mix against the general handler alone,
+then the per-call totals of modes 1 -> 2 and 2 -> 3 side by side.  Every
+result is checked bit for bit against the host libm, and every argument
+against its class's range.
 
 Usage: python scripts/trig_range_counts.py [trees=192] [tiles=2]
 """
@@ -36,11 +38,20 @@ CLASS = ("general", "mid", "small", "midlo", "wide")
 LIMIT = (math.inf, 2.42, 0.855, 1.44, 1e8)
 
 
-def handler(kind, c):
-    """The handler of a node's class (midlo is a cos class: a sin node never
-    gets it)."""
-    assert not (kind == "sin" and c == 3)
-    return kind.upper() if c == 0 else "%s_%s" % (kind.upper(), CLASS[c].upper())
+def handler(kind, c, mode=2):
+    """The handler of a node's class (modes 1 and 2: midlo is a cos class, a
+    sin node never gets it; mode 3: sin too, and mid and midlo are the bodies
+    with static lane roles)."""
+    assert mode == 3 or not (kind == "sin" and c == 3)
+    return kind.upper() if c == 0 else "%s_%s%s" % (
+        kind.upper(), CLASS[c].upper(), "3" if mode == 3 and c in (1, 3) else "")
+
+
+def handlers(mode):
+    """Every handler a node can get in `mode` (mode 1 picks a subset of mode
+    2's: the list is mode 2's there, the unused ones print no row)."""
+    return sorted({handler(k, c, mode) for k in ("sin", "cos") for c in range(5)
+                   if mode == 3 or not (k == "sin" and c == 3)})
 
 
 def f64(lo, hi):
@@ -93,19 +104,18 @@ def trig_calls(words, X):
 def count_mode(mode, n_trees, tiles, code, off, pop, calls_of, lo, hi, lines):
     """One GPE_TRIG_RANGES mode on the same calls: prints its table, returns
     (results that are not the host libm's, weighted totals per call)."""
-    names = sorted({handler(k, c) for k in ("sin", "cos") for c in range(5)
-                    if not (k == "sin" and c == 3)})
+    names = handlers(mode)
     spec = {h: {} for h in names}                # the node's class handler
     gen = {h: {} for h in names}                 # the general one, same calls
     calls = {h: 0 for h in names}
     bad = nan_calls = 0
     for i in range(n_trees):
         w = code[off[i]:off[i + 1]]
-        cls = _lib.debug_trig_classes(w, lo, hi, mode=mode)
+        cls = _lib.debug_trig_picks(w, lo, hi, mode=mode)
         got = calls_of[i]
         assert len(cls) == len(got)
         for c, (kind, arg) in zip(cls.tolist(), got):
-            h = handler(kind, c)
+            h = handler(kind, c, mode)
             f = math.sin if kind == "sin" else math.cos
             for t in range(tiles):
                 x = np.ascontiguousarray(arg[t * 128:(t + 1) * 128])
@@ -113,7 +123,7 @@ def count_mode(mode, n_trees, tiles, code, off, pop, calls_of, lo, hi, lines):
                 if not fin.all():
                     # general, or (mode 2) a NaN lane of a "bounded or NaN"
                     # value in mid / small / midlo: never an inf, never wide
-                    assert c == 0 or (mode == 2 and c in (1, 2, 3) and not np.isinf(x).any())
+                    assert c == 0 or (mode >= 2 and c in (1, 2, 3) and not np.isinf(x).any())
                     if c == 0:
                         continue
                     nan_calls += 1
@@ -174,19 +184,19 @@ def main():
         -1.0, 1.0, size=(tiles * 128, 10)).T)
     lo, hi = -np.ones(10), np.ones(10)
     calls_of = [trig_calls(code[off[i]:off[i + 1]], X) for i in range(n_trees)]
-    lines = {handler(k, c): asm_emu.handler_lines(handler(k, c))
-             for k in ("sin", "cos") for c in range(5) if not (k == "sin" and c == 3)}
+    lines = {h: asm_emu.handler_lines(h) for mode in (1, 2, 3) for h in handlers(mode)}
     bad = 0
     per_call = {}
-    for mode in (1, 2):
+    for mode in (1, 2, 3):
         b, per_call[mode] = count_mode(mode, n_trees, tiles, code, off, pop, calls_of,
                                        lo, hi, lines)
         bad += b
         print()
-    print("per average call, GPE_TRIG_RANGES=1 -> 2: VALU %.2f -> %.2f, fp64 %.2f -> %.2f, "
-          "SALU %.2f -> %.2f"
-          % (per_call[1]["valu"], per_call[2]["valu"], per_call[1]["valu_f64"],
-             per_call[2]["valu_f64"], per_call[1]["salu"], per_call[2]["salu"]))
+    for a, b in ((1, 2), (2, 3)):
+        print("per average call, GPE_TRIG_RANGES=%d -> %d: VALU %.2f -> %.2f, fp64 %.2f -> "
+              "%.2f, SALU %.2f -> %.2f"
+              % (a, b, per_call[a]["valu"], per_call[b]["valu"], per_call[a]["valu_f64"],
+                 per_call[b]["valu_f64"], per_call[a]["salu"], per_call[b]["salu"]))
     return 1 if bad else 0
 
 
