@@ -86,6 +86,20 @@ SIGNATURES = {
     "gpe_host_lexicase_par": (_I, [_P, _I64, _I64, _P, _I, ctypes.c_double,
                                    ctypes.c_uint64, _I64, _P, _P]),
     "gpe_lexicase_par_lds_values": (_I64, []),
+    "gpe_dalex": (_I, [_P, _P, _I64, _I64, ctypes.c_uint64, ctypes.c_double,
+                       _I, _I64, _P, _P]),
+    "gpe_dalex_bits": (_I, [_P, _P, _I64, _I64, ctypes.c_uint64,
+                            ctypes.c_double, _I, _I64, _P, _P]),
+    "gpe_dalex_weights": (_I, [_P, _I64, _I64, ctypes.c_uint64,
+                               ctypes.c_double, _P, _P]),
+    "gpe_dalex_sigma": (_I, [_P, _P, _I64, _I64, _P]),
+    "gpe_weighted_errors": (_I, [_P, _P, _I64, _I64, _P, _I64, _P]),
+    "gpe_last_dalex_ms": (_I, [_P, ctypes.POINTER(ctypes.c_float)]),
+    "gpe_host_dalex_weights": (_I, [_I64, _I64, ctypes.c_uint64,
+                                    ctypes.c_double, _P, _P]),
+    "gpe_host_dalex_sigma": (_I, [_P, _I64, _I64, _P]),
+    "gpe_host_dalex": (_I, [_P, _I64, _I64, ctypes.c_uint64, ctypes.c_double,
+                            _I, _I64, _P, _P]),
     "gpe_hit_group_counts": (_I, [_P, _P, _I64, _I64, _P, _I, _P]),
     "gpe_host_hit_group_counts": (_I, [_P, _I64, _I64, _P, _I, _P]),
     "gpe_last_hit_group_ms": (_I, [_P, ctypes.POINTER(ctypes.c_float)]),
@@ -536,7 +550,97 @@ def host_lexicase_par(values, maximise, k, seed, mode=0, epsilon=0.0):
     return out[:k], failed.value
 
 
-TRIG_CLASSES = ("general", "mid", "small")
+_U64 = 0xFFFFFFFFFFFFFFFF
+
+
+def _check_dalex(what, n, n_cases, k, pressure, k_name="k selections"):
+    """The sizes and the pressure of a DALex call, in the library's words."""
+    if n < 1 or n > 2 ** 31 - 1:
+        raise ValueError("%s: n = %d individuals (need 1 .. 2^31 - 1)"
+                         % (what, n))
+    if n_cases < 1 or n_cases > 2 ** 31 - 1:
+        raise ValueError("%s: n_cases = %d (need 1 .. 2^31 - 1)"
+                         % (what, n_cases))
+    if k < 0 or k > 2 ** 31 - 1:
+        raise ValueError("%s: %s = %d (need 0 .. 2^31 - 1)"
+                         % (what, k_name, k))
+    if pressure is not None and \
+            not (pressure >= 0.0 and math.isfinite(pressure)):
+        raise ValueError("%s: pressure must be finite and >= 0 (got %r)"
+                         % (what, pressure))
+
+
+def _dalex_values(what, values):
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    if values.ndim != 2:
+        raise ValueError("%s: values must be [n, n_cases] (got %d "
+                         "dimensions)" % (what, values.ndim))
+    return values
+
+
+def _dalex_sigma_arg(what, sigma, n_cases):
+    if sigma is None:
+        return None
+    sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+    if sigma.shape != (int(n_cases),):
+        raise ValueError("%s: sigma must have one entry per case (%d), got "
+                         "shape %r" % (what, n_cases, sigma.shape))
+    return sigma
+
+
+def host_dalex_weights(n_cases, k, seed, pressure, sigma=None):
+    """Host twin of :meth:`Context.dalex_weights` (CPU, no GPU): steps 1 - 4
+    of the DALex rule (include/gpeval.h) in plain C++ with libm →
+    ``float64[n_cases, k]``, case-major: column *s* holds selection *s*'s
+    effective weights.  *sigma* ``[n_cases]`` standardises (a zero gives
+    weight 0); None leaves the softmax weights."""
+    n_cases, k, pressure = int(n_cases), int(k), float(pressure)
+    _check_dalex("host_dalex_weights", 1, n_cases, k, pressure)
+    sigma = _dalex_sigma_arg("host_dalex_weights", sigma, n_cases)
+    out = np.zeros((n_cases, max(k, 1)), dtype=np.float64)
+    rc = load().gpe_host_dalex_weights(n_cases, k, int(seed) & _U64, pressure,
+                                       _ptr(sigma), _ptr(out))
+    if rc != 0:
+        raise GpeError("gpe_host_dalex_weights failed (%d)" % rc)
+    return out if k else out[:, :0]
+
+
+def host_dalex_sigma(values):
+    """Host twin of :meth:`Context.dalex_sigma` (CPU, no GPU): each case's
+    population standard deviation over the fit rows of *values*
+    ``[n, n_cases]`` (step 4 of the rule) → ``float64[n_cases]``."""
+    values = _dalex_values("host_dalex_sigma", values)
+    n, c = values.shape
+    _check_dalex("host_dalex_sigma", n, c, 0, None)
+    out = np.zeros(c, dtype=np.float64)
+    rc = load().gpe_host_dalex_sigma(_ptr(values), n, c, _ptr(out))
+    if rc != 0:
+        raise GpeError("gpe_host_dalex_sigma failed (%d)" % rc)
+    return out
+
+
+def host_dalex(values, k, seed, pressure, standardize=True):
+    """Host twin of :meth:`Context.dalex` (CPU, no GPU): the DALex rule of
+    include/gpeval.h on *values* ``[n, n_cases]`` (non-negative errors), every
+    score summed in ascending case order in fp64 → ``(indices int32[k],
+    failed)``: -1 where no row is fit, *failed* the first such selection or
+    -1.  ``ValueError`` for what the library refuses: an empty matrix,
+    ``k < 0``, a *pressure* that is negative, nan or infinite."""
+    values = _dalex_values("host_dalex", values)
+    n, c = values.shape
+    k, pressure = int(k), float(pressure)
+    _check_dalex("host_dalex", n, c, k, pressure)
+    out = np.zeros(max(k, 1), dtype=np.int32)
+    failed = ctypes.c_int64(-1)
+    rc = load().gpe_host_dalex(_ptr(values), n, c, int(seed) & _U64, pressure,
+                               1 if standardize else 0, k, _ptr(out),
+                               ctypes.byref(failed))
+    if rc != 0:
+        raise GpeError("gpe_host_dalex failed (%d)" % rc)
+    return out[:k], failed.value
+
+
+TRIG_CLASSES =("general", "mid", "small")
 # the classes GPE_TRIG_RANGES=2 and 3 (the default) pick handlers by
 TRIG_PICKED = TRIG_CLASSES + ("midlo", "wide")
 
@@ -1185,6 +1289,94 @@ class Context(object):
             int(seed) & 0xFFFFFFFFFFFFFFFF, int(k), _ptr(out),
             ctypes.byref(failed)), "gpe_lexicase_bits_par")
         return out[:int(k)], failed.value
+
+    def _values_arg(self, what, values):
+        """The *values* argument of the DALex calls → ``(rows, cases, n,
+        n_cases, ptr, keep)``: None is the resident per-case matrix, whose
+        sizes the library knows."""
+        if values is None:
+            return self.n_prog, self.n_cases, 0, 0, None, None
+        values = _dalex_values(what, values)
+        n, c = values.shape
+        return n, c, n, c, _ptr(values), values
+
+    def dalex(self, values, k, seed, pressure, standardize=True):
+        """gpe_dalex: k DALex selections (the rule: include/gpeval.h) on
+        ``values`` [n, n_cases] of non-negative errors (None: the last
+        run_cases / run_abserr_cases matrix) — weights on the device, one fp64
+        MFMA product with a fused argmin; no ``random`` draw is made.  Returns
+        (indices int32[k], failed): -1 where no row is fit, *failed* the first
+        such selection or -1.  Cost grows as n * n_cases * k."""
+        rows, cases, n, c, ptr, keep = self._values_arg("dalex", values)
+        out = np.zeros(max(int(k), 1), dtype=np.int32)
+        failed = ctypes.c_int64(-1)
+        self._check(self.lib.gpe_dalex(
+            self.h, ptr, n, c, int(seed) & _U64, float(pressure),
+            1 if standardize else 0, int(k), _ptr(out),
+            ctypes.byref(failed)), "gpe_dalex")
+        return out[:int(k)], failed.value
+
+    def dalex_bits(self, planes, n, n_cases, k, seed, pressure,
+                   standardize=True):
+        """gpe_dalex_bits: :meth:`dalex` on 0/1 hits with error ``1 - hit``.
+        *planes* as :meth:`lexicase_bits` takes them (None: the resident hit
+        planes)."""
+        rows, n, n_cases, cases, ptr, keep = self._planes_arg(
+            "dalex_bits", planes, n, n_cases)
+        out = np.zeros(max(int(k), 1), dtype=np.int32)
+        failed = ctypes.c_int64(-1)
+        self._check(self.lib.gpe_dalex_bits(
+            self.h, ptr, n, n_cases, int(seed) & _U64, float(pressure),
+            1 if standardize else 0, int(k), _ptr(out),
+            ctypes.byref(failed)), "gpe_dalex_bits")
+        return out[:int(k)], failed.value
+
+    def dalex_weights(self, n_cases, k, seed, pressure, sigma=None):
+        """gpe_dalex_weights → ``float64[n_cases, k]``: the effective weights
+        the device makes for k selections, case-major (column *s* is
+        selection *s*).  *sigma* ``[n_cases]`` standardises
+        (:meth:`dalex_sigma` gives the device's); None: the softmax
+        weights."""
+        n_cases, k = int(n_cases), int(k)
+        sigma = _dalex_sigma_arg("dalex_weights", sigma, n_cases)
+        out = np.zeros((max(n_cases, 1), max(k, 1)), dtype=np.float64)
+        self._check(self.lib.gpe_dalex_weights(
+            self.h, n_cases, k, int(seed) & _U64, float(pressure),
+            _ptr(sigma), _ptr(out)), "gpe_dalex_weights")
+        return out[:n_cases] if k else out[:n_cases, :0]
+
+    def dalex_sigma(self, values):
+        """gpe_dalex_sigma → ``float64[n_cases]``: each case's population
+        standard deviation over the fit rows, as :meth:`dalex` standardises
+        by.  *values* as :meth:`dalex`."""
+        rows, cases, n, c, ptr, keep = self._values_arg("dalex_sigma", values)
+        out = np.zeros(max(cases, 1), dtype=np.float64)
+        self._check(self.lib.gpe_dalex_sigma(self.h, ptr, n, c, _ptr(out)),
+                    "gpe_dalex_sigma")
+        return out[:cases]
+
+    def weighted_errors(self, values, weights):
+        """gpe_weighted_errors → ``float64[n, G]``: every row's sum of
+        ``weights[g][c] * values[i][c]``, *weights* float64 ``[G, n_cases]``
+        (or 1-D), any ``G >= 1``, checked by :func:`check_case_weights`.  A
+        row with an error that is not finite gives ``nan``.  *values* as
+        :meth:`dalex`."""
+        rows, cases, n, c, ptr, keep = self._values_arg("weighted_errors",
+                                                        values)
+        w = check_case_weights("weighted_errors", weights, cases)
+        G = w.shape[0]
+        out = np.zeros((max(rows, 1), max(G, 1)), dtype=np.float64)
+        self._check(self.lib.gpe_weighted_errors(
+            self.h, ptr, n, c, _ptr(w), G, _ptr(out)), "gpe_weighted_errors")
+        return out[:rows, :G]
+
+    def dalex_ms(self):
+        """Device ms of the last :meth:`dalex` / :meth:`dalex_bits` /
+        :meth:`weighted_errors` call's kernels."""
+        ms = ctypes.c_float(0.0)
+        self._check(self.lib.gpe_last_dalex_ms(self.h, ctypes.byref(ms)),
+                    "gpe_last_dalex_ms")
+        return float(ms.value)
 
     def hit_group_counts(self, planes, n, n_cases, masks):
         """gpe_hit_group_counts → ``int64[n, G]``: ``popcount(row & mask)``

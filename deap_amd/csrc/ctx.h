@@ -604,6 +604,28 @@ struct gpe_ctx {
   unsigned long long* d_hw_live = nullptr;
   size_t hw_live_cap = 0;
   float hw_ms = 0;                   // device events around the last call's kernels
+  // DALex selection and weighted error sums (dalex.h): the fit rows uint8[n],
+  // sigma double[n_cases], the effective weights case-major double[n_cases][k]
+  // (d_dlx_win: a caller's weights before their transposition), the argmin
+  // partials (score, individual) [ceil(n / 64)][k] and gpe_weighted_errors'
+  // sums double[n][G].  The matrix is d_case_t / d_lexp_vt (lexicase_par.h) or
+  // hit_matrix.h's Q; picks and the failing selection go through d_sel_out /
+  // d_lexp_failed.
+  uint8_t* d_dlx_fit = nullptr;
+  size_t dlx_fit_cap = 0;
+  double* d_dlx_sigma = nullptr;
+  size_t dlx_sigma_cap = 0;
+  double* d_dlx_wt = nullptr;
+  size_t dlx_wt_cap = 0;
+  double* d_dlx_win = nullptr;
+  size_t dlx_win_cap = 0;
+  double* d_dlx_ps = nullptr;
+  size_t dlx_ps_cap = 0;
+  int32_t* d_dlx_pi = nullptr;
+  size_t dlx_pi_cap = 0;
+  double* d_dlx_out = nullptr;
+  size_t dlx_out_cap = 0;
+  float dlx_ms = 0;                  // device events around the last call's kernels
   char* h_pin_vals = nullptr;        // pinned staging of gpe_run_values' copy back
   size_t h_pin_vals_cap = 0;
   float ms[3] = {0, 0, 0};

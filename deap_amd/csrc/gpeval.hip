@@ -1908,7 +1908,8 @@ void gpe_destroy(gpe_ctx* ctx) {
                   ctx->d_lexp_masks, ctx->d_lexp_counts, ctx->d_lexp_failed, ctx->d_lexp_cand,
                   ctx->d_lexp_vals, ctx->d_jump_asm_typed_hits, ctx->d_lab_planes,
                   ctx->d_hitgrp_masks, ctx->d_hitgrp_out, ctx->d_hw_w, ctx->d_hw_out,
-                  ctx->d_hw_cnt, ctx->d_hw_live};
+                  ctx->d_hw_cnt, ctx->d_hw_live, ctx->d_dlx_fit, ctx->d_dlx_sigma,
+                  ctx->d_dlx_wt, ctx->d_dlx_win, ctx->d_dlx_ps, ctx->d_dlx_pi, ctx->d_dlx_out};
   if (ctx->comm && rccl().ok) (void)rccl().comm_destroy(ctx->comm);
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -2907,6 +2908,7 @@ int gpe_run_values_bits(gpe_ctx* ctx, uint32_t* out_planes) {
 #include "case_bits.h"
 #include "case_informed.h"
 #include "lexicase_par.h"
+#include "dalex.h"
 #include "hit_groups.h"
 #include "hit_weights.h"
 

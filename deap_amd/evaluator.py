@@ -1031,6 +1031,8 @@ class GPUEvaluator(object):
         self._lex_batch = None
         # select_lexicase(parallel=True): the seed its last call drew
         self.last_lexicase_seed = None
+        # select_dalex: the seed its last call drew
+        self.last_dalex_seed = None
         # informed_subsample: each pick's distance to the nearest earlier one
         self.last_informed_distances = np.zeros(0, dtype=np.int32)
         # shared_hits: how many individuals solve each case
@@ -1586,6 +1588,102 @@ class GPUEvaluator(object):
         if failed >= 0:                   # random.choice([]) in the reference
             raise IndexError("Cannot choose from an empty sequence")
         return [individuals[i] for i in idx.tolist()]
+
+    def select_dalex(self, individuals, k, pressure, standardize=True):
+        """DALex selection (Ni, Ding and Spector 2024) of *k* individuals
+        from the per-case matrix the last :meth:`evaluate` / :meth:`map` left
+        on the GPU (``gpe_dalex`` / ``gpe_dalex_bits``): every selection draws
+        one normal importance score per case (standard deviation *pressure*,
+        the "particularity pressure"), turns the scores into weights with a
+        softmax and picks the individual with the smallest weighted sum of its
+        per-case errors.  A large *pressure* behaves like lexicase, a small
+        one like selection on the mean error.  With *standardize* every case
+        is divided by its standard deviation over the population first (a
+        constant case gets weight 0).  The *k* selections are one fp64 matrix
+        product on the GPU with a fused argmin; the cost grows as
+        ``n * n_cases * k``.
+
+        It works after :class:`SymbRegCaseAbsErrors` (either *cases* mode),
+        :class:`SymbRegCaseErrors` and the four hit-plane specs (a case's
+        error is then ``1 - hit``), and under :meth:`subsample`.  The checks
+        are :meth:`select_lexicase`'s, in its order: *individuals* must be the
+        batch of that last evaluation (``ValueError``), the first exception an
+        individual raised is raised here, ``k == 0`` returns ``[]`` before any
+        draw.  The only draw from ``random`` is ``seed =
+        random.getrandbits(64)``, kept in ``last_dalex_seed``; weights and
+        tie-breaks are SplitMix64 keys of it (the rule is in
+        include/gpeval.h, ``_lib.host_dalex`` is its host twin), so a seeded
+        run is reproducible.  An individual with an error that is not finite
+        is never picked; when nobody is left, ``IndexError`` as
+        ``random.choice([])``.  Nothing resident changes."""
+        pressure = float(pressure)
+        if not (pressure >= 0.0 and math.isfinite(pressure)):
+            raise ValueError("select_dalex: pressure must be finite and >= 0 "
+                             "(got %r)" % (pressure,))
+        individuals = list(individuals)
+        bits = getattr(self.spec, "hit_planes", False)
+
+        def own():
+            last = self._lex_batch[0]
+            if len(individuals) != len(last) or \
+                    any(a is not b for a, b in zip(individuals, last)):
+                raise ValueError(
+                    "select_dalex: individuals must be the batch of this "
+                    "evaluator's last evaluate / map, the same objects in "
+                    "the same order: the GPU holds that batch's per-case "
+                    "errors")
+        last, results = self._last_batch(
+            "select_dalex", True,
+            "this evaluator's last evaluate / map left no per-case matrix on "
+            "the GPU (its spec is %s; evaluate with SymbRegCaseAbsErrors, "
+            "SymbRegCaseErrors or BooleanCaseHits first)", own=own)
+        for res in results:
+            if isinstance(res, BaseException):
+                raise res
+        if k == 0:
+            return []
+        if not individuals:
+            raise IndexError("list index out of range")
+        seed = random.getrandbits(64)     # the only draw
+        self.last_dalex_seed = seed
+        if bits:
+            idx, failed = self.ctx.dalex_bits(None, 0, 0, k, seed, pressure,
+                                              standardize)
+        else:
+            idx, failed = self.ctx.dalex(None, k, seed, pressure, standardize)
+        if failed >= 0:                   # nobody is fit: random.choice([])
+            raise IndexError("Cannot choose from an empty sequence")
+        return [individuals[i] for i in idx.tolist()]
+
+    def weighted_errors(self, weights):
+        """Each individual's weighted sum of its per-case errors,
+        ``sum_c weights[c] * e[i, c]`` (``gpe_weighted_errors``, the DALex
+        product kernel with a store epilogue): ``float64[n]`` for 1-D
+        *weights* ``[n_cases]``, ``float64[n, G]`` for 2-D ``[G, n_cases]``
+        (one column per boosting round or sample-weight vector; any *G*).
+        The matrix is the one the last :meth:`evaluate` / :meth:`map` left on
+        the GPU with :class:`SymbRegCaseAbsErrors` or
+        :class:`SymbRegCaseErrors` (for hit planes see :meth:`weighted_hits`).
+        Every weight must be finite and ``>= 0`` (``ValueError``).  The sum
+        is within ``(n_cases + 1) * 2^-53`` relative of the exact one.  An
+        individual whose result is an exception, or with an error that is not
+        finite, gets ``nan``.  ``ValueError`` when the last evaluate / map
+        left no such matrix or another batch has been loaded since."""
+        last, results = self._last_batch(
+            "weighted_errors",
+            not getattr(self.spec, "hit_planes", False),
+            "this evaluator's last evaluate / map left no per-case errors on "
+            "the GPU (its spec is %s; evaluate with SymbRegCaseAbsErrors or "
+            "SymbRegCaseErrors first)")
+        one = np.ndim(weights) == 1
+        w = _lib.check_case_weights("weighted_errors", weights,
+                                    self.spec.n_cases)
+        n, G = len(last), w.shape[0]
+        out = np.zeros((n, G), dtype=np.float64)
+        if n and G:
+            out[:] = self.ctx.weighted_errors(None, w)
+            out[self._raised(results)] = np.nan
+        return out[:, 0] if one else out
 
     def last_case_hits(self):
         """``bool[n, n_cases]``: the hit matrix of the last

@@ -22,7 +22,7 @@ from operator import attrgetter, eq
 
 __all__ = ["initRepeat", "initIterate", "initCycle", "selRandom", "selBest",
            "selWorst", "selTournament", "selLexicase", "selEpsilonLexicase",
-           "selAutomaticEpsilonLexicase", "selLexicaseGPU", "selEpsilonLexicaseGPU",
+           "selAutomaticEpsilonLexicase", "selLexicaseGPU", "selEpsilonLexicaseGPU", "selDALexGPU",
            "selAutomaticEpsilonLexicaseGPU", "selTournamentGPU", "Statistics",
            "MultiStatistics",
            "Logbook", "HallOfFame", "identity"]
@@ -194,6 +194,38 @@ def selAutomaticEpsilonLexicaseGPU(individuals, k, device=None,
     if len(individuals) > AUTO_EPSILON_DEVICE_MAX:
         return selAutomaticEpsilonLexicase(individuals, k)
     return _lexicase_gpu(individuals, k, 2, device=device)
+
+
+def selDALexGPU(individuals, k, pressure, standardize=True, device=None):
+    """DALex selection (Ni, Ding and Spector 2024) on the individuals'
+    fitness tuples, one fitness value per case: ``gpe_dalex`` on the GPU
+    (:meth:`GPUEvaluator.select_dalex` is the same selection straight from
+    the resident per-case matrix).  Every selection draws a normal importance
+    score per case with standard deviation *pressure*, weights the cases by
+    the scores' softmax and picks the individual with the smallest weighted
+    error sum; with *standardize* each case is first divided by its standard
+    deviation over the population.  The error of a case is the negated
+    wvalue: a fitness weight of -1 minimises the value, +1 maximises it.  The
+    only draw from ``random`` is one ``getrandbits(64)``; ``k == 0`` returns
+    ``[]`` before it.  An individual with a value that is not finite is never
+    picked; when nobody is left, ``IndexError`` as ``random.choice([])``."""
+    import numpy as np
+    from . import _lib
+    from .evaluator import _default_device
+    if k == 0:
+        return []
+    if not individuals:
+        raise IndexError("list index out of range")
+    dev = _default_device() if device is None else device
+    if dev not in _LEX_CTX:
+        _LEX_CTX[dev] = _lib.Context(dev)
+    errors = -np.asarray([ind.fitness.wvalues for ind in individuals],
+                         dtype=np.float64)
+    idx, failed = _LEX_CTX[dev].dalex(errors, k, random.getrandbits(64),
+                                      pressure, standardize)
+    if failed >= 0:
+        raise IndexError("Cannot choose from an empty sequence")
+    return [individuals[i] for i in idx.tolist()]
 
 
 # round 1's name of selLexicaseGPU, kept for callers written against it

@@ -521,6 +521,119 @@ int gpe_host_lexicase_par(const double* values, int64_t n, int64_t n_cases,
  * keeps in LDS; larger candidate sets go through device scratch. */
 int64_t gpe_lexicase_par_lds_values(void);
 
+/* DALex selection (Ni, Ding and Spector 2024): selection by weighted sums of
+ * the per-case errors.  Every selection draws one normal importance score per
+ * case, turns the scores into weights with a softmax and picks the individual
+ * with the smallest weighted error sum.  A large `pressure` (the spread of the
+ * scores, "particularity pressure") behaves like lexicase, a small one like
+ * selection on the mean.  The k selections are one matrix product
+ * S = E W'^T, n x n_cases x k fp64 FMAs on v_mfma_f64_16x16x4_f64; the cost
+ * grows as n * n_cases * k.  As gpe_lexicase_par, the caller makes one draw, a
+ * 64-bit seed, and everything follows from it by this rule.
+ *
+ * K(i) is gpe_lexicase_par's SplitMix64 key (K(0) = 0xE220A8397B1DCDAF,
+ * K(1) = 0x6E789E6AA1B965F4 for seed = 0), and K2(i) the same function with
+ * seed ^ 0xD1B54A32D192ED03 in seed's place.  For selection s in [0, k) and
+ * case c in [0, C), with j = s * C + c as a uint64:
+ * 1. Importance.  u1 = ((K(2j) >> 11) + 1) * 2^-53, u2 = (K(2j + 1) >> 11) *
+ *    2^-53, z = sqrt(-2 ln u1) * cos(2 pi u2) (2 pi the double
+ *    6.283185307179586, times u2 in fp64), I = pressure * z.  pressure is
+ *    finite and >= 0 (pressure * 8.6 must not overflow: |z| <= 8.6).
+ * 2. Softmax.  m = max_c I, x_c = exp(I_c - m), w_c = x_c / sum_c x_c, the
+ *    sum taken in ascending c in fp64.
+ * 3. Fit rows.  A row of the error matrix is fit when every one of its errors
+ *    is finite.  Unfit rows take part in nothing below.
+ * 4. Standardisation (standardize != 0).  sigma_c is the population standard
+ *    deviation (ddof 0) of case c over the m fit rows: mean = hi(sum e) / m,
+ *    sigma = sqrt(hi(sum (e - mean)^2) / m), each sum a double-double sum of
+ *    256 strided partials (fit row i goes into partial i % 256 in ascending i,
+ *    by gpe_run_abserr's two_sum step) merged by a fixed tree of its dd_add.
+ *    The effective weight is w'_c = w_c / sigma_c, and 0 where sigma_c == 0;
+ *    without standardisation w' = w.  The case mean is not subtracted: that
+ *    adds a constant per selection and cannot change the argmin, so the product
+ *    runs on the raw non-negative errors and every term is >= 0.
+ * 5. Score and pick.  S(i, s) = sum_c w'_{s,c} * e_{i,c} in fp64.  The pick is
+ *    the fit row with the smallest (S, K2(s * n + i), i), compared
+ *    lexicographically; the tie key is computed only where two scores are
+ *    equal, so duplicates are picked uniformly and not by position.  With no
+ *    fit row out[s] = -1 and *failed is the smallest such s (-1 if none), as
+ *    gpe_lexicase_par.
+ * 6. Order independence.  The bits of S(i, s) depend only on row i's values,
+ *    column s's weights and C — not on n, k, the row's position or the tile it
+ *    lands in: a wave walks all C cases of its tile in steps of 4 (the MFMA's
+ *    k), there is no split over the cases and no atomic combine.  Identical
+ *    rows get identical scores.  (The host twin sums in ascending c; the two
+ *    agree bit for bit where every partial sum is representable, and within
+ *    (C + 1) * 2^-53 relative otherwise, every term being >= 0.)
+ * On 0/1 hit planes the error of a case is 1 - hit.
+ *
+ * gpe_dalex: values is a HOST double[n][n_cases] of non-negative errors, or
+ * NULL for the per-case matrix of the last gpe_run_cases /
+ * gpe_run_abserr_cases (n, n_cases are then the context's; GPE_E_STATE as
+ * gpe_lexicase_par, and when another batch was loaded since).  out is
+ * int32[k].  n outside 1 .. 2^31 - 1, n_cases outside 1 .. 2^31 - 1 or k
+ * outside 0 .. 2^31 - 1: GPE_E_INVALID with a message; a nan, negative or
+ * infinite pressure: GPE_E_ARG.  k == 0 does nothing.  Ragged n, n_cases and k
+ * are the kernel's business (operand edges are zero-filled, rows >= n masked);
+ * there is no limit beyond memory.  The call disturbs nothing else: the
+ * resident fitness, the per-case matrix, the hit planes and the active case
+ * set stay as they were. */
+int gpe_dalex(gpe_ctx* ctx, const double* values, int64_t n, int64_t n_cases,
+              uint64_t seed, double pressure, int standardize, int64_t k,
+              int32_t* out, int64_t* failed);
+
+/* The same rule on 0/1 hits, e = 1 - hit (every row is fit).  planes is
+ * gpe_lexicase_bits_par's HOST matrix uint32[n][ceil(n_cases / 32)], or NULL
+ * for the resident hit planes (gpe_run_hit_planes /
+ * gpe_run_typed_hit_planes; GPE_E_STATE as there).  The product reads the
+ * case-major planes and expands a bit to 1.0 - bit in the operand load; sigma
+ * comes from the same kernel as gpe_dalex's, so the picks are those of
+ * gpe_dalex on the matrix unpacked to doubles. */
+int gpe_dalex_bits(gpe_ctx* ctx, const uint32_t* planes, int64_t n,
+                   int64_t n_cases, uint64_t seed, double pressure,
+                   int standardize, int64_t k, int32_t* out, int64_t* failed);
+
+/* The effective weights of k selections, read back: out_Wt is a HOST
+ * double[n_cases][k] (case-major, as the product reads them).  sigma is a
+ * HOST double[n_cases] (step 4; gpe_dalex_sigma gives the device's), or NULL
+ * for w' = w.  Argument errors as gpe_dalex. */
+int gpe_dalex_weights(gpe_ctx* ctx, int64_t n_cases, int64_t k, uint64_t seed,
+                      double pressure, const double* sigma, double* out_Wt);
+
+/* sigma of step 4 as the device computes it: out_sigma is a HOST
+ * double[n_cases]; values as gpe_dalex. */
+int gpe_dalex_sigma(gpe_ctx* ctx, const double* values, int64_t n,
+                    int64_t n_cases, double* out_sigma);
+
+/* Weighted sums of the errors themselves: out[i][g] = sum_c weights[g][c] *
+ * e[i][c], the product kernel with a store epilogue.  values as gpe_dalex;
+ * weights is a HOST double[G][n_cases], any G >= 1, every weight finite and
+ * >= 0 (else GPE_E_ARG); out is a HOST double[n][G].  An unfit row (step 3)
+ * gives nan.  The sum's order is step 6's: within (n_cases + 1) * 2^-53
+ * relative of the exact sum, and exact where every partial sum is
+ * representable.  Sizes out of range (G < 1 too): GPE_E_INVALID. */
+int gpe_weighted_errors(gpe_ctx* ctx, const double* values, int64_t n,
+                        int64_t n_cases, const double* weights, int64_t G,
+                        double* out);
+
+/* Device time of the last gpe_dalex / gpe_dalex_bits / gpe_weighted_errors'
+ * kernels in ms (fit rows, sigma, weights, product and fold; the upload, the
+ * transposition and the copies back are outside). */
+int gpe_last_dalex_ms(const gpe_ctx* ctx, float* ms);
+
+/* Host twins (no GPU) in plain C++ with libm: the weights of steps 1 - 4
+ * (out_Wt double[n_cases][k]), sigma of step 4 and the selection of gpe_dalex
+ * with every score summed in ascending c in fp64.  GPE_E_INVALID for the
+ * arguments the device calls refuse and for a NULL matrix or output. */
+int gpe_host_dalex_weights(int64_t n_cases, int64_t k, uint64_t seed,
+                           double pressure, const double* sigma,
+                           double* out_Wt);
+int gpe_host_dalex_sigma(const double* values, int64_t n, int64_t n_cases,
+                         double* out_sigma);
+int gpe_host_dalex(const double* values, int64_t n, int64_t n_cases,
+                   uint64_t seed, double pressure, int standardize, int64_t k,
+                   int32_t* out, int64_t* failed);
+
 /* Masked counts of a hit matrix: out[i][g] = popcount(row_i & mask_g), an
  * individual's hits inside each of G case groups.  With the label plane as
  * the one mask the count is a classifier's true positives (and hits - tp its
