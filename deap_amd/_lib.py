@@ -100,6 +100,12 @@ SIGNATURES = {
     "gpe_host_dalex_sigma": (_I, [_P, _I64, _I64, _P]),
     "gpe_host_dalex": (_I, [_P, _I64, _I64, ctypes.c_uint64, ctypes.c_double,
                             _I, _I64, _P, _P]),
+    "gpe_nd_sort": (_I, [_P, _P, _P, _I64, _I64, _I64, _I, _P, _P,
+                         ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    "gpe_last_nd_sort_ms": (_I, [_P, ctypes.POINTER(ctypes.c_float)]),
+    "gpe_last_nd_sort_fronts": (_I, [_P, ctypes.POINTER(_I64)]),
+    "gpe_host_nd_sort": (_I, [_P, _P, _I64, _I64, _I64, _I, _P, _P,
+                              ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     "gpe_hit_group_counts": (_I, [_P, _P, _I64, _I64, _P, _I, _P]),
     "gpe_host_hit_group_counts": (_I, [_P, _I64, _I64, _P, _I, _P]),
     "gpe_last_hit_group_ms": (_I, [_P, ctypes.POINTER(ctypes.c_float)]),
@@ -638,6 +644,61 @@ def host_dalex(values, k, seed, pressure, standardize=True):
     if rc != 0:
         raise GpeError("gpe_host_dalex failed (%d)" % rc)
     return out[:k], failed.value
+
+
+ND_SORT_MAX_OBJECTIVES = 32
+
+
+def _nd_sort_args(what, w, mult, k):
+    """The arguments of a non-dominated sort, checked in the library's words
+    → ``(w float64[n, m], mult int32[n] or None, k)``."""
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if w.ndim != 2:
+        raise ValueError("%s: w must be [n, m] (got %d dimensions)"
+                         % (what, w.ndim))
+    n, m = w.shape
+    if n < 1 or n > 2 ** 31 - 1:
+        raise ValueError("%s: n = %d rows (need 1 .. 2^31 - 1)" % (what, n))
+    if m < 1 or m > ND_SORT_MAX_OBJECTIVES:
+        raise ValueError("%s: m = %d objectives (need 1 .. %d)"
+                         % (what, m, ND_SORT_MAX_OBJECTIVES))
+    k = int(k)
+    if k < 0:
+        raise ValueError("%s: k = %d (need >= 0)" % (what, k))
+    if mult is not None:
+        mult = np.ascontiguousarray(mult, dtype=np.int32)
+        if mult.shape != (n,):
+            raise ValueError("%s: mult must have one entry per row (%d), got "
+                             "shape %r" % (what, n, mult.shape))
+    return w, mult, k
+
+
+def _nd_sort_result(order, front_end, n_fronts):
+    """``order`` cut at ``front_end`` → a list of int32 arrays, one a front."""
+    ends = front_end[:n_fronts].tolist()
+    return [order[a:b].copy() for a, b in zip([0] + ends[:-1], ends)]
+
+
+def host_nd_sort(w, k, mult=None, first_front_only=False):
+    """Host twin of :meth:`Context.nd_sort` (CPU, no GPU): the non-dominated
+    sorting rule of include/gpeval.h in plain C++ → a list of int32 arrays,
+    the rows of each front in the rule's order.  ``ValueError`` for what the
+    library refuses: an empty matrix, m outside 1 .. 32, ``k < 0``, a nan, a
+    multiplicity below 1."""
+    w, mult, k = _nd_sort_args("host_nd_sort", w, mult, k)
+    n, m = w.shape
+    order = np.zeros(n, dtype=np.int32)
+    front_end = np.zeros(n, dtype=np.int64)
+    nf, nr = ctypes.c_int64(0), ctypes.c_int64(0)
+    rc = load().gpe_host_nd_sort(_ptr(w), _ptr(mult), n, m, k,
+                                 1 if first_front_only else 0, _ptr(order),
+                                 _ptr(front_end), ctypes.byref(nf),
+                                 ctypes.byref(nr))
+    if rc == GPE_E_ARG:
+        raise ValueError("host_nd_sort: a nan in w or a multiplicity < 1")
+    if rc != 0:
+        raise GpeError("gpe_host_nd_sort failed (%d)" % rc)
+    return _nd_sort_result(order, front_end, nf.value)
 
 
 TRIG_CLASSES =("general", "mid", "small")
@@ -1377,6 +1438,44 @@ class Context(object):
         self._check(self.lib.gpe_last_dalex_ms(self.h, ctypes.byref(ms)),
                     "gpe_last_dalex_ms")
         return float(ms.value)
+
+    def nd_sort(self, w, k, mult=None, first_front_only=False):
+        """gpe_nd_sort: the non-dominated fronts of the rows of *w* float64
+        ``[n, m]`` (weighted fitness values, one row per distinct fitness; the
+        rule: include/gpeval.h) until they cover ``min(total, k)``
+        individuals, *mult* int32 ``[n]`` giving the individuals per row
+        (None: one each).  Returns a list of int32 arrays, the rows of each
+        front in the reference's order.  ``ValueError`` for the sizes the
+        library refuses, for a nan and for a multiplicity below 1.  Nothing
+        resident on the context is disturbed; cost grows as m * n^2."""
+        w, mult, k = _nd_sort_args("nd_sort", w, mult, k)
+        n, m = w.shape
+        order = np.zeros(n, dtype=np.int32)
+        front_end = np.zeros(n, dtype=np.int64)
+        nf, nr = ctypes.c_int64(0), ctypes.c_int64(0)
+        rc = self.lib.gpe_nd_sort(self.h, _ptr(w), _ptr(mult), n, m, k,
+                                  1 if first_front_only else 0, _ptr(order),
+                                  _ptr(front_end), ctypes.byref(nf),
+                                  ctypes.byref(nr))
+        if rc == GPE_E_ARG:
+            msg = self.lib.gpe_last_error(self.h)
+            raise ValueError(msg.decode() if msg else "nd_sort: bad values")
+        self._check(rc, "gpe_nd_sort")
+        return _nd_sort_result(order, front_end, nf.value)
+
+    def nd_sort_ms(self):
+        """Device ms of the last :meth:`nd_sort` call's kernels."""
+        ms = ctypes.c_float(0.0)
+        self._check(self.lib.gpe_last_nd_sort_ms(self.h, ctypes.byref(ms)),
+                    "gpe_last_nd_sort_ms")
+        return float(ms.value)
+
+    def nd_sort_fronts(self):
+        """The number of fronts of the last :meth:`nd_sort` call."""
+        nf = ctypes.c_int64(0)
+        self._check(self.lib.gpe_last_nd_sort_fronts(self.h, ctypes.byref(nf)),
+                    "gpe_last_nd_sort_fronts")
+        return int(nf.value)
 
     def hit_group_counts(self, planes, n, n_cases, masks):
         """gpe_hit_group_counts → ``int64[n, G]``: ``popcount(row & mask)``

@@ -105,7 +105,7 @@ LIB_HEADERS = ("lower_core.h", "trig_ranges.h", "host_pool.h", "bigint_host.h", 
                "rccl_layer.h", "select_dev.h", "ctx.h", "fb_kernels.h", "asm_kernels.h",
                "f_eval_asm_body.h", "planner.h", "exact_run.h", "moments.h", "abserr.h",
                "case_subset.h", "hit_matrix.h", "case_bits.h", "case_informed.h", "lexicase_par.h",
-               "dalex.h", "typed_hits.h", "hit_groups.h", "hit_weights.h")
+               "dalex.h", "nd_sort.h", "typed_hits.h", "hit_groups.h", "hit_weights.h")
 
 
 def needs_build():

@@ -626,6 +626,29 @@ struct gpe_ctx {
   double* d_dlx_out = nullptr;
   size_t dlx_out_cap = 0;
   float dlx_ms = 0;                  // device events around the last call's kernels
+  // Non-dominated sorting (nd_sort.h), all of it the call's own so that nothing
+  // resident is touched: the matrix objective-major double[m][n], the appended
+  // and the sorted front keys uint64[n], the order int32[n], the dominator
+  // counts int32[n] (-1: ranked), the multiplicities, the two counters (rows
+  // ranked, individuals covered) and the sort's scratch.
+  double* d_nd_wt = nullptr;
+  size_t nd_wt_cap = 0;
+  unsigned long long* d_nd_keys = nullptr;
+  size_t nd_keys_cap = 0;
+  unsigned long long* d_nd_sorted = nullptr;
+  size_t nd_sorted_cap = 0;
+  int32_t* d_nd_order = nullptr;
+  size_t nd_order_cap = 0;
+  int32_t* d_nd_cnt = nullptr;
+  size_t nd_cnt_cap = 0;
+  int32_t* d_nd_mult = nullptr;
+  size_t nd_mult_cap = 0;
+  unsigned long long* d_nd_ctr = nullptr;
+  size_t nd_ctr_cap = 0;
+  char* d_nd_tmp = nullptr;
+  size_t nd_tmp_cap = 0;
+  float nd_ms = 0;                   // the last call's kernels (device events)
+  int64_t nd_fronts = 0;             // ... and its number of fronts
   char* h_pin_vals = nullptr;        // pinned staging of gpe_run_values' copy back
   size_t h_pin_vals_cap = 0;
   float ms[3] = {0, 0, 0};

@@ -1909,7 +1909,9 @@ void gpe_destroy(gpe_ctx* ctx) {
                   ctx->d_lexp_vals, ctx->d_jump_asm_typed_hits, ctx->d_lab_planes,
                   ctx->d_hitgrp_masks, ctx->d_hitgrp_out, ctx->d_hw_w, ctx->d_hw_out,
                   ctx->d_hw_cnt, ctx->d_hw_live, ctx->d_dlx_fit, ctx->d_dlx_sigma,
-                  ctx->d_dlx_wt, ctx->d_dlx_win, ctx->d_dlx_ps, ctx->d_dlx_pi, ctx->d_dlx_out};
+                  ctx->d_dlx_wt, ctx->d_dlx_win, ctx->d_dlx_ps, ctx->d_dlx_pi, ctx->d_dlx_out,
+                  ctx->d_nd_wt, ctx->d_nd_keys, ctx->d_nd_sorted, ctx->d_nd_order,
+                  ctx->d_nd_cnt, ctx->d_nd_mult, ctx->d_nd_ctr, ctx->d_nd_tmp};
   if (ctx->comm && rccl().ok) (void)rccl().comm_destroy(ctx->comm);
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -2909,6 +2911,7 @@ int gpe_run_values_bits(gpe_ctx* ctx, uint32_t* out_planes) {
 #include "case_informed.h"
 #include "lexicase_par.h"
 #include "dalex.h"
+#include "nd_sort.h"
 #include "hit_groups.h"
 #include "hit_weights.h"
 

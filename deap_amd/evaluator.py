@@ -937,12 +937,26 @@ class GPUEvaluator(object):
     """
 
     def __init__(self, pset, spec, device=None, machine=None,
-                 trig_leaves=True, precision="fp64"):
+                 trig_leaves=True, precision="fp64", size_objective=False):
         """*precision* ``"fp64"`` (default) matches the reference (1e-12
         relative MSE); ``"fp32"`` evaluates the trees in single precision
-        for throughput, with the agreement DESIGN.md §4 states."""
+        for throughput, with the agreement DESIGN.md §4 states.
+
+        *size_objective* True appends ``len(individual)`` (an ADF
+        individual: the sum of its trees' lengths) to every fitness tuple
+        :meth:`evaluate`, :meth:`map` and a call return — the second
+        objective of a parsimony run under ``tools.selNSGA2GPU``.  Exception
+        entries pass through unchanged.  Specs whose tuple is one value per
+        case (``cases="host"``, :class:`SymbRegCaseErrors`) refuse it."""
         if precision not in ("fp64", "fp32"):
             raise ValueError("precision must be 'fp64' or 'fp32'")
+        if size_objective and (getattr(spec, "per_case", False) or
+                               getattr(spec, "cases", None) == "host"):
+            raise ValueError(
+                "size_objective: the fitness tuple of %s is one value per "
+                "case (lexicase selection reads it as such); a size has no "
+                "place in it" % type(spec).__name__)
+        self.size_objective = bool(size_objective)
         if getattr(spec, "typed_planes", False) and precision != "fp64":
             raise NotImplementedError(
                 "%s needs precision='fp64': the typed core's hit planes are "
@@ -1444,7 +1458,19 @@ class GPUEvaluator(object):
 
     def evaluate(self, individuals):
         """Fitness tuple, or the exception instance the reference would raise,
-        for every individual (in order)."""
+        for every individual (in order).  With ``size_objective`` the tuples
+        end with the individual's size."""
+        out = self._evaluate_spec(individuals)
+        if not self.size_objective:
+            return out
+        # (a new list: select_lexicase's record keeps the spec's own tuples)
+        adf = isinstance(self.pset, (list, tuple))
+        return [res if isinstance(res, BaseException) else
+                tuple(res) + (sum(len(t) for t in ind) if adf else len(ind),)
+                for ind, res in zip(individuals, out)]
+
+    def _evaluate_spec(self, individuals):
+        """:meth:`evaluate` without the size objective: the spec's tuples."""
         batch = self.lower_on_device(individuals, keep=False) \
             if self.device_lowering else None
         if batch is None:

@@ -9,8 +9,12 @@ GP examples wire around the evaluation hot path:
   (reference ``deap/tools/selection.py:12-69``) and the lexicase family
   (``:214-320``, fed by per-case fitness from ``SymbRegCaseErrors``) —
   consumers of the fitness the GPU evaluator produces;
-* ``Statistics``/``MultiStatistics``/``Logbook``/``HallOfFame``
-  (reference ``deap/tools/support.py:154-589``).
+* NSGA-II: ``selNSGA2``/``sortNondominated``/``assignCrowdingDist``/
+  ``selTournamentDCD`` (reference ``deap/tools/emo.py:15-195``), with
+  ``sortNondominatedGPU``/``selNSGA2GPU`` doing the N^2 dominance tests on
+  the GPU and returning the same lists;
+* ``Statistics``/``MultiStatistics``/``Logbook``/``HallOfFame``/
+  ``ParetoFront`` (reference ``deap/tools/support.py:154-641``).
 """
 import random
 from bisect import bisect_right
@@ -23,9 +27,11 @@ from operator import attrgetter, eq
 __all__ = ["initRepeat", "initIterate", "initCycle", "selRandom", "selBest",
            "selWorst", "selTournament", "selLexicase", "selEpsilonLexicase",
            "selAutomaticEpsilonLexicase", "selLexicaseGPU", "selEpsilonLexicaseGPU", "selDALexGPU",
-           "selAutomaticEpsilonLexicaseGPU", "selTournamentGPU", "Statistics",
-           "MultiStatistics",
-           "Logbook", "HallOfFame", "identity"]
+           "selAutomaticEpsilonLexicaseGPU", "selTournamentGPU",
+           "selNSGA2", "sortNondominated", "assignCrowdingDist",
+           "selTournamentDCD", "sortNondominatedGPU", "selNSGA2GPU",
+           "Statistics", "MultiStatistics",
+           "Logbook", "HallOfFame", "ParetoFront", "identity"]
 
 
 # ----------------------------------------------------------------- init ----
@@ -254,6 +260,240 @@ def selTournamentGPU(individuals, k, tournsize, fit_attr="fitness",
     return [individuals[i] for i in idx.tolist()]
 
 
+# --------------------------------------------------------------- NSGA-II ----
+def _nsga2_cut(fronts, k):
+    """All fronts but the last, then the last one's most isolated members
+    (descending crowding distance, Python's stable ``sorted``) up to *k*."""
+    chosen = [ind for front in fronts[:-1] for ind in front]
+    room = k - len(chosen)
+    if room > 0:
+        by_distance = sorted(fronts[-1], reverse=True,
+                             key=attrgetter("fitness.crowding_dist"))
+        chosen.extend(by_distance[:room])
+    return chosen
+
+
+def selNSGA2(individuals, k, nd="standard"):
+    """NSGA-II selection (reference emo.py:15-50): the non-dominated fronts
+    that cover *k* individuals, every front given its crowding distances, the
+    last front cut by descending distance.  Draws nothing from ``random``.
+    ``nd='log'`` (the reference's ``sortLogNondominated``) is not restated."""
+    if nd == "log":
+        raise NotImplementedError("selNSGA2: nd='log' is not implemented")
+    if nd != "standard":
+        raise Exception("selNSGA2: unknown non-dominated sorting method %r" % (nd,))
+    fronts = sortNondominated(individuals, k)
+    for front in fronts:
+        assignCrowdingDist(front)
+    return _nsga2_cut(fronts, k)
+
+
+def sortNondominated(individuals, k, first_front_only=False):
+    """Fast non-dominated sorting (reference emo.py:53-117): O(M N^2) calls
+    of ``Fitness.dominates`` over the distinct fitnesses, taken in the order
+    they first appear; fronts until ``min(len(individuals), k)`` individuals
+    are ranked.  Inside a front the fitnesses stand in the order in which
+    their last dominator of the previous front, in that front's order,
+    released them (front 0: first-appearance order)."""
+    if k == 0:
+        return []
+    members = {}               # fitness -> its individuals, in input order
+    for ind in individuals:
+        members.setdefault(ind.fitness, []).append(ind)
+    fits = list(members)
+    n = len(fits)
+    dominators = [0] * n                  # how many fitnesses dominate a
+    dominated = [[] for _ in range(n)]    # whom a dominates, ascending
+    for a in range(n):
+        for b in range(a + 1, n):
+            if fits[a].dominates(fits[b]):
+                dominators[b] += 1
+                dominated[a].append(b)
+            elif fits[b].dominates(fits[a]):
+                dominators[a] += 1
+                dominated[b].append(a)
+
+    def expand(front):
+        return [ind for a in front for ind in members[fits[a]]]
+
+    front = [a for a in range(n) if dominators[a] == 0]
+    fronts = [expand(front)]
+    ranked = len(fronts[0])
+    if first_front_only:
+        return fronts
+    target = min(len(individuals), k)
+    while ranked < target:
+        released = []
+        for p in front:
+            for d in dominated[p]:
+                dominators[d] -= 1
+                if dominators[d] == 0:
+                    released.append(d)
+        front = released
+        fronts.append(expand(front))
+        ranked += len(fronts[-1])
+    return fronts
+
+
+def assignCrowdingDist(individuals):
+    """Set ``fitness.crowding_dist`` on every individual of one front
+    (reference emo.py:119-143): per objective, a stable sort of the order the
+    previous objective left, ``inf`` for the two ends, ``(next - prev) /
+    (nobj * (max - min))`` added for the others; an objective whose ends are
+    equal adds nothing."""
+    n = len(individuals)
+    if n == 0:
+        return
+    values = [ind.fitness.values for ind in individuals]
+    nobj = len(values[0])
+    dist = [0.0] * n
+    order = list(range(n))
+    for j in range(nobj):
+        order.sort(key=lambda i: values[i][j])
+        low, high = values[order[0]][j], values[order[-1]][j]
+        dist[order[0]] = float("inf")
+        dist[order[-1]] = float("inf")
+        if high == low:
+            continue
+        norm = nobj * float(high - low)
+        for pos in range(1, n - 1):
+            dist[order[pos]] += (values[order[pos + 1]][j]
+                                 - values[order[pos - 1]][j]) / norm
+    for ind, d in zip(individuals, dist):
+        ind.fitness.crowding_dist = d
+
+
+def selTournamentDCD(individuals, k):
+    """Dominance / crowding-distance tournaments (reference emo.py:145-195):
+    two ``random.sample`` permutations of the individuals, per step of four
+    two pairs of each; the dominating one of a pair wins, else the one with
+    the larger ``crowding_dist``, else ``random.random() <= 0.5`` picks the
+    first."""
+    n = len(individuals)
+    if k > n:
+        raise ValueError("selTournamentDCD: k = %d exceeds the %d individuals"
+                         % (k, n))
+    if k == n and k % 4 != 0:
+        raise ValueError("selTournamentDCD: k == len(individuals) must be a "
+                         "multiple of four (got %d)" % k)
+
+    def winner(a, b):
+        if a.fitness.dominates(b.fitness):
+            return a
+        if b.fitness.dominates(a.fitness):
+            return b
+        da, db = a.fitness.crowding_dist, b.fitness.crowding_dist
+        if da < db:
+            return b
+        if da > db:
+            return a
+        return a if random.random() <= 0.5 else b
+
+    perms = (random.sample(individuals, n), random.sample(individuals, n))
+    chosen = []
+    for i in range(0, k, 4):
+        for perm in perms:
+            chosen.append(winner(perm[i], perm[i + 1]))
+            chosen.append(winner(perm[i + 2], perm[i + 3]))
+    return chosen
+
+
+def _nd_fronts_gpu(individuals, k, first_front_only, device):
+    """The fronts of :func:`sortNondominatedGPU` and the weighted values
+    float64 ``[len(individuals), nobj]`` they were ranked by."""
+    import numpy as np
+    from . import _lib
+    from .evaluator import _default_device
+    groups = {}                # wvalues -> members, in first-appearance order
+    for i, ind in enumerate(individuals):
+        groups.setdefault(ind.fitness.wvalues, []).append(i)
+    if not groups:
+        return [[]], np.zeros((0, 0))
+    w = np.asarray(list(groups.keys()), dtype=np.float64)
+    if w.ndim != 2 or np.isnan(w).any():
+        raise ValueError("sortNondominatedGPU: a fitness value is nan (or the "
+                         "fitnesses differ in length)")
+    members = list(groups.values())
+    mult = np.asarray([len(g) for g in members], dtype=np.int32)
+    dev = _default_device() if device is None else device
+    if dev not in _LEX_CTX:
+        _LEX_CTX[dev] = _lib.Context(dev)
+    rows = _LEX_CTX[dev].nd_sort(w, k, mult, first_front_only)
+    fronts = [[i for r in front.tolist() for i in members[r]]
+              for front in rows]
+    wall = np.empty((len(individuals), w.shape[1]), dtype=np.float64)
+    for r, g in enumerate(members):
+        wall[g] = w[r]
+    return fronts, wall
+
+
+def sortNondominatedGPU(individuals, k, first_front_only=False, device=None):
+    """Drop-in for :func:`sortNondominated` (reference emo.py:53-117) with
+    the dominance tests on the GPU (``gpe_nd_sort``; the rule is in
+    include/gpeval.h): the same list of fronts, the same order inside each.
+    The individuals are grouped by their ``wvalues`` in a dict (``0.0`` and
+    ``-0.0`` fall together, as under ``Fitness.__hash__`` / ``__eq__``), the
+    distinct rows ranked in one call and expanded again, each group's members
+    in input order.  A nan fitness value raises ``ValueError`` (the
+    reference's order there depends on its sort's internals)."""
+    if k == 0:
+        return []
+    fronts, _ = _nd_fronts_gpu(individuals, k, first_front_only, device)
+    return [[individuals[i] for i in front] for front in fronts]
+
+
+def _crowding_dist(values):
+    """:func:`assignCrowdingDist`'s distances of one front, vectorised:
+    *values* float64 ``[n, nobj]`` (``fitness.values``, nan-free) →
+    float64 ``[n]`` with the same bits."""
+    import numpy as np
+    n, nobj = values.shape
+    dist = np.zeros(n, dtype=np.float64)
+    perm = np.arange(n)
+    with np.errstate(all="ignore"):
+        for i in range(nobj):
+            # the stable sort of the order the previous objective left
+            perm = perm[np.argsort(values[perm, i], kind="stable")]
+            col = values[perm, i]
+            dist[perm[0]] = np.inf
+            dist[perm[-1]] = np.inf
+            if col[-1] == col[0]:
+                continue
+            norm = nobj * float(col[-1] - col[0])
+            if n > 2:
+                dist[perm[1:-1]] += (col[2:] - col[:-2]) / norm
+    return dist
+
+
+def selNSGA2GPU(individuals, k, device=None):
+    """Drop-in for :func:`selNSGA2` (reference emo.py:15-50) with the
+    non-dominated sorting on the GPU (:func:`sortNondominatedGPU`): the same
+    *k* individuals in the same order, the same ``fitness.crowding_dist`` on
+    every individual of the fronts it went through.  The crowding distances
+    are computed per front on the host in numpy (O(M N log N), off the N^2
+    path) and the last front is cut with Python's own stable ``sorted``, so
+    ties and nan distances (from infinite values) order as in the reference.
+    Nothing is drawn from ``random``; a nan fitness value raises
+    ``ValueError``; ``k == 0`` returns ``[]``."""
+    import numpy as np
+    if k == 0:
+        return []
+    fronts, wall = _nd_fronts_gpu(individuals, k, False, device)
+    if not individuals:
+        return []
+    with np.errstate(all="ignore"):     # Fitness.values: wvalues / weights
+        values = wall / np.asarray(individuals[0].fitness.weights,
+                                   dtype=np.float64)
+    pareto_fronts = []
+    for front in fronts:
+        dist = _crowding_dist(values[front]).tolist()
+        members = [individuals[i] for i in front]
+        for ind, d in zip(members, dist):
+            ind.fitness.crowding_dist = d
+        pareto_fronts.append(members)
+    return _nsga2_cut(pareto_fronts, k)
+
+
 # -------------------------------------------------------------- support ----
 def identity(obj):
     return obj
@@ -445,3 +685,33 @@ class HallOfFame(object):
 
     def __str__(self):
         return str(self.items)
+
+
+class ParetoFront(HallOfFame):
+    """Every non-dominated individual that ever lived, sorted
+    lexicographically as a :class:`HallOfFame` without a size limit
+    (reference support.py:591-641).  A newcomer is scanned against the
+    members in order: a member that dominates it ends the scan (unless it has
+    already beaten one), members it dominates leave, and a member of equal
+    fitness that is ``similar`` makes it a twin, which stays out."""
+
+    def __init__(self, similar=eq):
+        HallOfFame.__init__(self, None, similar)
+
+    def update(self, population):
+        for ind in population:
+            dominated = twin = False
+            beaten = []
+            for i, member in enumerate(self):
+                if not beaten and member.fitness.dominates(ind.fitness):
+                    dominated = True
+                    break
+                if ind.fitness.dominates(member.fitness):
+                    beaten.append(i)
+                elif ind.fitness == member.fitness and self.similar(ind, member):
+                    twin = True
+                    break
+            for i in reversed(beaten):
+                self.remove(i)
+            if not (dominated or twin):
+                self.insert(ind)

@@ -634,6 +634,57 @@ int gpe_host_dalex(const double* values, int64_t n, int64_t n_cases,
                    uint64_t seed, double pressure, int standardize, int64_t k,
                    int32_t* out, int64_t* failed);
 
+/* Non-dominated sorting (the ranking of NSGA-II selection, Deb et al. 2002):
+ * the fronts the reference's sortNondominated returns, in its order, from N^2
+ * dominance tests on the GPU.  The rule:
+ *
+ * Input.  w is a HOST double[n][m] of weighted fitness values (wvalues), one
+ * row per distinct fitness; mult int32[n] (or NULL for all 1) says how many
+ * individuals share each row, every entry >= 1.
+ * 1. Dominance.  Row p dominates row d iff w[p][j] >= w[d][j] for every j and
+ *    w[p][j] > w[d][j] for some j (Fitness.dominates).  Equal rows do not
+ *    dominate each other; infinities compare as in IEEE; -0.0 == 0.0.
+ * 2. Front 0 is the rows nobody dominates, in ascending row index.
+ * 3. Front r + 1.  Every unranked row loses one from its dominator count for
+ *    each of its dominators in front r; the rows that reach 0 form front
+ *    r + 1, ordered by the key (P, d) ascending: P the largest position
+ *    within front r among d's dominators there, d the row index.  (The order
+ *    in which the reference appends to its next front: a row is appended when
+ *    the last of its dominators, in front order, is processed, and each
+ *    dominator's list of dominated rows is in ascending index.)
+ * 4. Stop after the front with which the individuals covered (the sum of
+ *    mult over the ranked rows) reach min(total individuals, k); with
+ *    first_front_only, after front 0.  k == 0 gives no fronts.
+ * 5. m == 1 needs no peeling: the fronts are the distinct values in
+ *    descending order, equal rows of one front in ascending index.  It is one
+ *    sort, so a chain of a million fronts is not a million launches.
+ * Counts and positions are integers and every combine is an integer atomic
+ * add or a sort of distinct keys: the result does not depend on scheduling.
+ *
+ * order is int32[n]: the rows of front 0, then front 1, ...; front_end is
+ * int64[n]: the cumulative ends of the fronts, *n_fronts of them; *n_ranked
+ * (= front_end[*n_fronts - 1], or 0) rows of `order` are written.  n outside
+ * 1 .. 2^31 - 1, m outside 1 .. 32 or k < 0: GPE_E_INVALID with a message.  A
+ * nan in w (the reference's order there depends on its sort's internals) or a
+ * mult < 1: GPE_E_ARG.  The matrix is uploaded (n * m doubles) into buffers
+ * of the call's own: nothing resident is disturbed.  One small readback per
+ * front (rows ranked, individuals covered); the cost grows as m * n^2. */
+int gpe_nd_sort(gpe_ctx* ctx, const double* w, const int32_t* mult, int64_t n,
+                int64_t m, int64_t k, int first_front_only, int32_t* order,
+                int64_t* front_end, int64_t* n_fronts, int64_t* n_ranked);
+
+/* Device time of the last gpe_nd_sort's kernels in ms (counts, peels, sorts;
+ * the upload and the readbacks are outside), and its number of fronts. */
+int gpe_last_nd_sort_ms(const gpe_ctx* ctx, float* ms);
+int gpe_last_nd_sort_fronts(const gpe_ctx* ctx, int64_t* fronts);
+
+/* Host twin (no GPU) of gpe_nd_sort: the same rule in plain C++, the same
+ * argument errors (without a message). */
+int gpe_host_nd_sort(const double* w, const int32_t* mult, int64_t n,
+                     int64_t m, int64_t k, int first_front_only,
+                     int32_t* order, int64_t* front_end, int64_t* n_fronts,
+                     int64_t* n_ranked);
+
 /* Masked counts of a hit matrix: out[i][g] = popcount(row_i & mask_g), an
  * individual's hits inside each of G case groups.  With the label plane as
  * the one mask the count is a classifier's true positives (and hits - tp its

@@ -17,7 +17,7 @@ cp deap_amd/csrc/gpeval.hip deap_amd/csrc/lower_core.h deap_amd/csrc/trig_ranges
    deap_amd/csrc/trig_dev.h deap_amd/csrc/exact_int.h deap_amd/csrc/rccl_layer.h deap_amd/csrc/select_dev.h \
    deap_amd/csrc/ctx.h deap_amd/csrc/fb_kernels.h deap_amd/csrc/asm_kernels.h deap_amd/csrc/f_eval_asm_body.h \
    deap_amd/csrc/planner.h deap_amd/csrc/exact_run.h deap_amd/csrc/moments.h deap_amd/csrc/abserr.h \
-   deap_amd/csrc/case_subset.h deap_amd/csrc/case_bits.h deap_amd/csrc/case_informed.h deap_amd/csrc/lexicase_par.h deap_amd/csrc/dalex.h \
+   deap_amd/csrc/case_subset.h deap_amd/csrc/case_bits.h deap_amd/csrc/case_informed.h deap_amd/csrc/lexicase_par.h deap_amd/csrc/dalex.h deap_amd/csrc/nd_sort.h \
    deap_amd/csrc/typed_hits.h deap_amd/csrc/hit_groups.h deap_amd/csrc/hit_weights.h deap_amd/csrc/hit_matrix.h \
    deap_amd/csrc/gp_asm_core32*.inc \
    "$tmp/deap_amd/csrc/"
